@@ -12,6 +12,12 @@ Multi-GPU: the path shards by independent frame pairs; every rank aligns its own
 B pairs, no data-path collective; scaling is "weak".
 
 Prints ONE JSON line on rank 0 (see the driver contract in the task statement).
+
+A plain run of the headline workload (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps
+and prints the line; its CPU baseline, secondary legs (8x8 patches, the 1024-pair step), one-pair latency and the
+measured copy bandwidth run only with --full.  On the other workloads --full likewise turns on what --no-cpu-baseline /
+--no-secondary govern and the copy bandwidth.  --dump-outputs DIR writes the results of the headline's last timed step
+as DIR/<name>.npy (float64), so that two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -1547,10 +1553,18 @@ def parse_args(argv=None):
     ap.add_argument("--stream-workers", type=int, default=0, help="host threads per lock-step group")
     ap.add_argument("--whole-sets", action="store_true", help="with --workload seeds: the timed leg is the batch over RESIDENT keyframe columns "
                     "(svoh_features_upload once; SVOH_BATCH_WHOLE_SETS: tile order from the upload, no per-frame binning)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="the measurements beside the headline figure as well: the CPU baselines and secondary legs (what --no-cpu-baseline / "
+                         "--no-secondary switch off; the default line's 8x8 patches and 1024-pair step), its one-pair latency, the measured copy bandwidth")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last one as DIR/<name>.npy (float64; --workload align)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the 8x8-patch leg that the default line carries as `secondary`")
-    return ap.parse_args(argv)
+                    help="with --full: skip the secondary legs (the default line's `secondary` and `step_of_1024`)")
+    args = ap.parse_args(argv)
+    if not args.full:   # a plain run: the timed leg alone
+        args.no_cpu_baseline = args.no_secondary = True
+    return args
 
 
 def free_port():
@@ -1623,7 +1637,12 @@ def bench_launch_check(args, dist, rank, world, comm_dev):
 
 
 def main(argv=None):
+    global _COPY_BW
     args = parse_args(argv)
+    if not args.full:
+        _COPY_BW = {}   # a plain run: measured_copy_bandwidth() answers None without measuring
+    if args.dump_outputs and args.workload != "align":
+        raise SystemExit("bench.py: --dump-outputs writes the headline workload's outputs (--workload align) only")
     rank, local_rank, world = du.env_world()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # not under torchrun: be the launcher (before anything touches the GPU), relay the workers' exit code
@@ -1684,7 +1703,8 @@ def main(argv=None):
     # are exactly two each, so that step ends with the slowest pair and measures a tail, not the kernel's rate (profiles/r06_align_batch_size_sweep.txt: 1.17 ms
     # per 1024 problems at 1024, 1.04 at 2048, 0.94 at 4096).  The 1024-pair step stays in the line as `step_of_1024`.
     P, N, B = args.patch, args.features, (args.problems or 4096)
-    out, shared = run_align(args, ctx, dist, rank, world, dev, comm_dev, P, N, B, None, not args.no_cpu_baseline and world == 1)
+    out, shared = run_align(args, ctx, dist, rank, world, dev, comm_dev, P, N, B, None, not args.no_cpu_baseline and world == 1,
+                            dump_dir=args.dump_outputs)
     # the 8x8-patch configuration north_star quotes its roofline target on, carried in the same line (same frame
     # pairs, same launch shape; its own features because the border margin depends on the patch size)
     if P == 4 and not args.no_secondary and not args.problems and N == 2000 and args.min_level == 0 and args.max_level == 4:
@@ -1713,7 +1733,21 @@ def main(argv=None):
         dist.destroy_process_group()
 
 
-def run_align(args, ctx, dist, rank, world, dev, comm_dev, P, N, B, shared, with_cpu, steps=None):
+def dump_align_results(dump_dir, res, rank, world):
+    """--dump-outputs: what a caller of svoh_sparse_align_batch receives for the last timed step, one float64 array per field
+    of svoh_align_result, one row per problem (DIR/<field>.npy; DIR/<field>_rank<r>.npy for the ranks of a multi-GPU run)."""
+    os.makedirs(dump_dir, exist_ok=True)
+    arrays = {"T_icur_iref": np.array([fe.se3_to_numpy(r.T_icur_iref) for r in res]),   # q (w x y z), t (x y z)
+              "status": [r.status for r in res], "n_fts_to_track": [r.n_fts_to_track for r in res],
+              "alpha": [r.alpha for r in res], "beta": [r.beta for r in res],
+              "iters": [list(r.iters) for r in res], "n_meas": [list(r.n_meas) for r in res],
+              "chi2": [list(r.chi2) for r in res], "n_patch_iters": [r.n_patch_iters for r in res]}
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, name + suffix + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def run_align(args, ctx, dist, rank, world, dev, comm_dev, P, N, B, shared, with_cpu, steps=None, dump_dir=None):
     """The headline workload at patch size P: W warm-up + K timed steps of one launch over B frame pairs."""
     steps = steps or args.steps
     opt = capi.default_align_options(max_level=args.max_level, min_level=args.min_level, patch_size=P)
@@ -1755,17 +1789,20 @@ def run_align(args, ctx, dist, rank, world, dev, comm_dev, P, N, B, shared, with
         n_timed += n_hist.value
     kernel_ms_sum *= steps / float(max(1, n_timed))
 
-    # latency of ONE frame pair of the same workload (outside the timed region): what a single camera stream sees
-    one_arr = (capi.svoh_align_problem * 1)(problems[0])
+    if dump_dir:
+        dump_align_results(dump_dir, res, rank, world)
+    # latency of ONE frame pair of the same workload (outside the timed region, --full): what a single camera stream sees
     lat_call, lat_kern = [], []
-    for k in range(12):
-        t1 = time.perf_counter()
-        ctx.sparse_align(opt, one_arr)
-        t2 = time.perf_counter()
-        ctx.lib.svoh_sparse_align_last_kernel_ms(ctx.h, ctypes.byref(kern_ms))
-        if k >= 2:
-            lat_call.append((t2 - t1) * 1e3)
-            lat_kern.append(kern_ms.value)
+    if args.full:
+        one_arr = (capi.svoh_align_problem * 1)(problems[0])
+        for k in range(12):
+            t1 = time.perf_counter()
+            ctx.sparse_align(opt, one_arr)
+            t2 = time.perf_counter()
+            ctx.lib.svoh_sparse_align_last_kernel_ms(ctx.h, ctypes.byref(kern_ms))
+            if k >= 2:
+                lat_call.append((t2 - t1) * 1e3)
+                lat_kern.append(kern_ms.value)
 
     n_sel = sum(r.n_fts_to_track for r in res)
     # whole-job numbers: MAX of the elapsed time, SUM of the patches all ranks aligned
@@ -1823,7 +1860,7 @@ def run_align(args, ctx, dist, rank, world, dev, comm_dev, P, N, B, shared, with
                                "trans_m_max": float(np.max([e[1] for e in errs]))},
             "solver_failures": n_bad,
             "one_frame_pair_latency_ms": {"blocking_call": float(np.median(lat_call)), "kernel": float(np.median(lat_kern)),
-                                          "note": "one problem of the same workload, several workgroups per problem"},
+                                          "note": "one problem of the same workload, several workgroups per problem"} if lat_call else None,
             "roofline": roofline("sparse_align_kernel<%d,256,false,false>" % P, kernel_ms, alg,
                                  "align:B%d:N%d:P%d:L%d-%d" % (B, N, P, args.max_level, args.min_level),
                                  patch_iterations=patch_iters,

@@ -85,3 +85,26 @@ def test_every_workload_choice_has_a_bench_function():
     table = re.search(r'out = \{(.*?)\}\[args.workload\]', src, re.S).group(1)
     dispatched = set(re.findall(r'"([a-z0-9-]+)":', table)) | {"align"}
     assert choices == dispatched, (choices ^ dispatched)
+
+
+def test_plain_run_leaves_the_side_measurements_to_full():
+    """`bench.py --gpus 1 --steps K --warmup W` times the headline steps and nothing else: the CPU baselines and the
+    secondary legs run with --full only (where --no-cpu-baseline / --no-secondary still switch them off one by one)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.no_cpu_baseline and a.no_secondary and a.dump_outputs is None and a.steps == 7
+    a = bench.parse_args(["--full"])
+    assert a.full and not a.no_cpu_baseline and not a.no_secondary
+    a = bench.parse_args(["--full", "--no-secondary", "--dump-outputs", "out"])
+    assert a.full and not a.no_cpu_baseline and a.no_secondary and a.dump_outputs == "out"
+
+
+def test_dump_outputs_refuses_a_workload_it_does_not_cover(tmp_path):
+    """--dump-outputs is refused up front (before any GPU call) for a workload whose outputs it does not write"""
+    r = _run_bench(["--workload", "klt", "--steps", "1", "--dump-outputs", str(tmp_path / "d")], {})
+    # bench.py's own refusal (exit 1, its message), not argparse's of an unknown option (exit 2)
+    assert r.returncode == 1 and "--workload align" in r.stderr and r.stdout.strip() == "", (r.returncode, r.stderr[-2000:])
+    assert not (tmp_path / "d").exists()

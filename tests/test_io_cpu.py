@@ -235,7 +235,9 @@ def test_map_and_key_point_mirrors_host_logic():
     assert out.returncode == 0 and "PASS" in out.stdout, out.stdout + out.stderr
 
 
-REF_PARAM = "/root/reference/examples/param"
+# the reference's own configuration files (examples/param/{pinhole.yaml, calib/euroc_mono.yaml, calib/euroc_stereo.yaml,
+# frontend_imu/euroc_stereo_imu.yaml}), stored unchanged as fixtures: settings only, no code
+REF_PARAM = os.path.join(ROOT, "tests", "golden", "param")
 
 
 def _dump(what, path):
@@ -246,10 +248,9 @@ def _dump(what, path):
     return dict(l.split(" ", 1) for l in out.stdout.strip().splitlines())
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PARAM), reason="the reference tree exists in the build container only")
 def test_reference_configuration_files_parse_to_survey_appendix_a():
-    """The loader on the reference's OWN files (read in place, never copied): examples/param/pinhole.yaml,
-    calib/euroc_mono.yaml, calib/euroc_stereo.yaml, frontend_imu/euroc_stereo_imu.yaml -> the values of SURVEY.md
+    """The loader on the reference's OWN files (tests/golden/param: copies of examples/param/pinhole.yaml,
+    calib/euroc_mono.yaml, calib/euroc_stereo.yaml, frontend_imu/euroc_stereo_imu.yaml) -> the values of SURVEY.md
     Appendix A (the loader had only ever been fed YAML the tests wrote)."""
     # --- calib/euroc_mono.yaml: 752x480 pinhole + radtan (examples/param/calib/euroc_mono.yaml:8-21)
     rig = _dump("rig", os.path.join(REF_PARAM, "calib", "euroc_mono.yaml"))
