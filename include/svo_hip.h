@@ -87,15 +87,18 @@ typedef struct svoh_se3 {
 } svoh_se3;
 
 typedef enum svoh_distortion {
-  SVOH_DISTORTION_NONE = 0,   /* vk::cameras::NoDistortion */
-  SVOH_DISTORTION_RADTAN = 1  /* vk::cameras::RadialTangentialDistortion k1 k2 p1 p2 */
+  SVOH_DISTORTION_NONE = 0,         /* vk::cameras::NoDistortion */
+  SVOH_DISTORTION_RADTAN = 1,       /* vk::cameras::RadialTangentialDistortion k1 k2 p1 p2 */
+  SVOH_DISTORTION_EQUIDISTANT = 2,  /* vk::cameras::EquidistantDistortion k1 k2 k3 k4 (Kannala-Brandt; YAML "equidistant") */
+  SVOH_DISTORTION_ATAN = 3          /* vk::cameras::AtanDistortion s (the FOV model; YAML "fisheye").  The reference has no
+                                     * Jacobian for it: every entry that would evaluate one returns SVOH_ERR_UNSUPPORTED */
 } svoh_distortion;
 
 /* vk::cameras::PinholeProjection<Distortion>
  * (src/vikit/vikit_cameras/include/vikit/cameras/implementation/pinhole_projection.hpp:10-64) */
 typedef struct svoh_camera {
   double fx, fy, cx, cy;
-  double d[4];          /* k1 k2 p1 p2 for RADTAN, ignored for NONE */
+  double d[4];          /* k1 k2 p1 p2 for RADTAN, k1 k2 k3 k4 for EQUIDISTANT, s in d[0] for ATAN, ignored for NONE */
   int32_t distortion;   /* svoh_distortion */
   int32_t width, height;
   int32_t reserved;
@@ -106,8 +109,9 @@ typedef struct svoh_camera {
  * can be restated against the device code and not only against the host compilation of the same header:
  *   px[2i..]     = PinholeProjection::project3(xyz[3i..])                        pinhole_projection.hpp:44-64
  *   J[6i..]      = its 2x3 Jacobian, row-major (diag(fx,fy) * distortion.jacobian(uv) * d(uv)/d(xyz))
- *   f_back[3i..] = PinholeProjection::backProject3(px[2i..]) (radtan: five fixed-point iterations)  :30-42
- * Host pointers; J and f_back may be NULL. */
+ *   f_back[3i..] = PinholeProjection::backProject3(px[2i..]) (radtan and equidistant: five fixed-point iterations;
+ *                  equidistant at exactly (cx, cy) is tan(0)/0 = NaN, as in the reference)  :30-42
+ * Host pointers; J and f_back may be NULL.  ATAN with J != NULL: SVOH_ERR_UNSUPPORTED (the reference has no Jacobian). */
 int svoh_camera_maths(svoh_ctx* ctx, const svoh_camera* cam, int n, const double* xyz, double* px, double* J,
                       double* f_back);
 

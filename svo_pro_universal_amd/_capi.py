@@ -13,6 +13,7 @@ SVOH_MAX_LEVELS = 8
 SVOH_MAX_CAMS = 4
 
 SVOH_OK = 0
+SVOH_ERR_UNSUPPORTED = -5   # svoh_status: e.g. a camera model an entry does not support
 SVOH_MEM_HOST = 0
 SVOH_MEM_DEVICE = 1
 SVOH_MEM_STAGED = 2
@@ -22,6 +23,8 @@ SVOH_MEM_HOST_PINNED = 3
 
 SVOH_DISTORTION_NONE = 0
 SVOH_DISTORTION_RADTAN = 1
+SVOH_DISTORTION_EQUIDISTANT = 2
+SVOH_DISTORTION_ATAN = 3
 
 SVOH_HALFSAMPLE_REFERENCE = 0
 SVOH_HALFSAMPLE_SCALAR = 1

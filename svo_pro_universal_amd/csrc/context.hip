@@ -5,6 +5,7 @@
 // (src/svo_common/src/frame.cpp:372-386) -> vk::halfSample
 // (src/vikit/vikit_common/src/vision.cpp:19-44 SSE2 rule, :73-111 dispatch and
 // scalar rule).  Integer work: results are bit-identical to the reference's.
+#include <cmath>
 #include <cstdarg>
 #include <algorithm>
 #include <cstring>
@@ -413,6 +414,25 @@ __global__ __launch_bounds__(64) void camera_maths_kernel(const svoh_camera cam,
   double Jl[6];
   project3_jacobian(cm, p, Jl);
   for (int k = 0; k < 6; ++k) J[6 * i + k] = Jl[k];
+  const Vec3 f = back_project3(cm, u, v);
+  f_back[3 * i] = f.x; f_back[3 * i + 1] = f.y; f_back[3 * i + 2] = f.z;
+}
+
+// the same for the wide camera family (svoh_math.h, CamModelWide); J == NULL: no Jacobian (ATAN has none)
+__global__ __launch_bounds__(64) void camera_maths_wide_kernel(const svoh_camera cam, int n, const double* xyz, double* px, double* J, double* f_back)
+{
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const CamModelWide cm = load_camera_wide(cam);
+  const Vec3 p = { xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2] };
+  double u, v;
+  project3(cm, p, u, v);
+  px[2 * i] = u; px[2 * i + 1] = v;
+  if (J) {
+    double Jl[6];
+    project3_jacobian(cm, p, Jl);
+    for (int k = 0; k < 6; ++k) J[6 * i + k] = Jl[k];
+  }
   const Vec3 f = back_project3(cm, u, v);
   f_back[3 * i] = f.x; f_back[3 * i + 1] = f.y; f_back[3 * i + 2] = f.z;
 }
@@ -906,15 +926,23 @@ int svoh_camera_maths(svoh_ctx* ctx, const svoh_camera* cam, int n, const double
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, cam && xyz && px && n >= 1 && n <= (1 << 20), "bad arguments");
-  SVOH_REQUIRE(ctx, cam->distortion == SVOH_DISTORTION_NONE || cam->distortion == SVOH_DISTORTION_RADTAN, "unsupported distortion model");
+  SVOH_REQUIRE(ctx, camera_is_known(*cam), "unsupported distortion model");
+  SVOH_REQUIRE(ctx, cam->distortion != SVOH_DISTORTION_ATAN || (cam->d[0] != 0.0 && std::isfinite(cam->d[0])),
+               "ATAN (fisheye) camera: s = d[0] must be finite and non-zero");
+  if (J && !camera_has_jacobian(*cam))
+    return set_error(ctx, SVOH_ERR_UNSUPPORTED, "the ATAN (fisheye) camera has no Jacobian (AtanDistortion::jacobian): pass J = NULL");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   // [xyz 3n | px 2n | J 6n | f 3n] doubles on the device
   const size_t nd = (size_t)n;
   SVOH_HIP_TRY(ctx, ctx->d_scratch2.reserve(14 * nd * sizeof(double)));
   double* d = static_cast<double*>(ctx->d_scratch2.ptr);
   SVOH_HIP_TRY(ctx, hipMemcpyAsync(d, xyz, 3 * nd * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(camera_maths_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, *cam, n, d, d + 3 * nd, d + 5 * nd,
-                     d + 11 * nd);
+  if (camera_is_narrow(*cam))
+    hipLaunchKernelGGL(camera_maths_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, *cam, n, d, d + 3 * nd, d + 5 * nd,
+                       d + 11 * nd);
+  else
+    hipLaunchKernelGGL(camera_maths_wide_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, *cam, n, d, d + 3 * nd,
+                       J ? d + 5 * nd : nullptr, d + 11 * nd);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(ctx, SVOH_ERR_HIP, "camera_maths launch failed: %s", hipGetErrorString(e));
   SVOH_HIP_TRY(ctx, hipMemcpyAsync(px, d + 3 * nd, 2 * nd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

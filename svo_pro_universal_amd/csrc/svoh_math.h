@@ -1,7 +1,7 @@
 // svoh_math.h -- small fixed-size double-precision maths shared by host and
 // device code of libsvo_hip: unit quaternions / rigid transforms with the
-// semantics of the reference's minkindr types, the pinhole (+radtan) camera,
-// and an 8x8 pivoted LDL^T solve with Eigen-3.4 semantics.
+// semantics of the reference's minkindr types, the pinhole camera (+radtan;
+// +equidistant / atan as the wide family, CamModelWide), and an 8x8 pivoted LDL^T solve with Eigen-3.4 semantics.
 //
 // Reference behaviour restated here (paths relative to the reference tree):
 //   3rd/minkindr/include/kindr/minimal/implementation/rotation-quaternion-inl.h
@@ -10,6 +10,7 @@
 //       :79-84 (ctor from 6-vector), :155-168, :212-238
 //   src/vikit/vikit_cameras/include/vikit/cameras/implementation/pinhole_projection.hpp:30-64
 //   src/vikit/vikit_cameras/include/vikit/cameras/radial_tangential_distortion.h:46-106
+//   src/vikit/vikit_cameras/include/vikit/cameras/equidistant_distortion.h:37-166, atan_distortion.h
 //   src/vikit/vikit_solver/include/vikit/solver/implementation/mini_least_squares_solver.hpp:253-262
 #pragma once
 
@@ -252,6 +253,173 @@ SVOH_HD Vec3 back_project3(const CamModel& c, double u, double v)
   }
   Vec3 r = { x, y, 1.0 };
   return r;
+}
+
+// ---- the wide camera family: EQUIDISTANT | ATAN, and NONE | RADTAN as above ---------------------------------------
+// CamModel and the three functions above are the narrow family (NONE | RADTAN), compiled into the kernels as they
+// always were.  The wide models need atan / tan / sqrt inside the projection; they get a type of their own, so that a
+// kernel instantiated for CamModelWide carries them and one instantiated for CamModel does not.
+//   src/vikit/vikit_cameras/include/vikit/cameras/equidistant_distortion.h:37-121, 145-166
+//   src/vikit/vikit_cameras/include/vikit/cameras/atan_distortion.h (initializeParameters, distort, undistort)
+struct CamModelWide : CamModel {
+  double k3, k4;                  // EQUIDISTANT: k1 k2 (CamModel) k3 k4 = d[0..3]
+  double s_inv, tans, tans_inv;   // ATAN: s = d[0] (CamModel::k1), AtanDistortion::initializeParameters
+};
+
+SVOH_HD CamModelWide load_camera_wide(const svoh_camera& c)
+{
+  CamModelWide m;
+  m.fx = c.fx; m.fy = c.fy; m.cx = c.cx; m.cy = c.cy;
+  m.k1 = c.d[0]; m.k2 = c.d[1]; m.p1 = c.d[2]; m.p2 = c.d[3];
+  m.k3 = c.d[2]; m.k4 = c.d[3];
+  m.distortion = c.distortion; m.width = c.width; m.height = c.height;
+  m.s_inv = m.tans = m.tans_inv = 0.0;
+  if (c.distortion == SVOH_DISTORTION_ATAN) {
+    m.s_inv = 1.0 / c.d[0];
+    m.tans = 2.0 * tan(c.d[0] / 2.0);
+    m.tans_inv = 1.0 / m.tans;
+  }
+  return m;
+}
+
+// load_camera / load_camera_wide by the kernel's camera type
+template <class Cam> SVOH_HD Cam load_camera_as(const svoh_camera& c);
+template <> SVOH_HD CamModel load_camera_as<CamModel>(const svoh_camera& c) { return load_camera(c); }
+template <> SVOH_HD CamModelWide load_camera_as<CamModelWide>(const svoh_camera& c) { return load_camera_wide(c); }
+
+SVOH_HD double equidistant_thetad(const CamModelWide& c, double theta)
+{
+  const double theta2 = theta * theta;
+  const double theta4 = theta2 * theta2;
+  const double theta6 = theta4 * theta2;
+  const double theta8 = theta4 * theta4;
+  return theta * (1.0 + c.k1 * theta2 + c.k2 * theta4 + c.k3 * theta6 + c.k4 * theta8);
+}
+
+constexpr double kEquidistantRThresh = 1e-8;   // EquidistantDistortion::kRThresh
+
+SVOH_HD void equidistant_distort(const CamModelWide& c, double& x, double& y)
+{
+  const double r = sqrt(x * x + y * y);
+  if (r < kEquidistantRThresh) return;
+  const double theta = atan(r);
+  const double scaling = equidistant_thetad(c, theta) / r;
+  x *= scaling;
+  y *= scaling;
+}
+
+// EquidistantDistortion::jacobian, row-major 2x2
+SVOH_HD void equidistant_jacobian(const CamModelWide& c, double x, double y, double& J00, double& J01, double& J10, double& J11)
+{
+  const double r = sqrt(x * x + y * y);
+  if (r < kEquidistantRThresh) { J00 = 1.0; J01 = 0.0; J10 = 0.0; J11 = 1.0; return; }
+  const double inv_r = 1.0 / r;
+  const double r2 = r * r;
+  const double dr_du = x * inv_r;
+  const double dr_dv = y * inv_r;
+  const double theta = atan(r);
+  const double dtheta_dr = 1.0 / (1 + r * r);
+  const double thetad = equidistant_thetad(c, theta);
+  const double theta2 = theta * theta;
+  const double theta4 = theta2 * theta2;
+  const double theta6 = theta4 * theta2;
+  const double theta8 = theta4 * theta4;
+  const double dthetad_dtheta = 1 + 3 * c.k1 * theta2 + 5 * c.k2 * theta4 + 7 * c.k3 * theta6 + 9 * c.k4 * theta8;
+  const double dthetad_dr = dthetad_dtheta * dtheta_dr;
+  const double scaling = thetad / r;
+  const double dscaling_du = (dthetad_dr * dr_du * r - dr_du * thetad) / r2;
+  const double dscaling_dv = (dthetad_dr * dr_dv * r - dr_dv * thetad) / r2;
+  J00 = dscaling_du * x + scaling;
+  J01 = dscaling_dv * x;
+  J10 = dscaling_du * y;
+  J11 = dscaling_dv * y + scaling;
+}
+
+// five fixed-point iterations, then tan(theta) / theta_d: NaN at theta_d == 0, as in the reference
+SVOH_HD void equidistant_undistort(const CamModelWide& c, double& x, double& y)
+{
+  const double thetad = sqrt(x * x + y * y);
+  double theta = thetad;
+  for (int i = 0; i < 5; ++i) {
+    const double theta2 = theta * theta;
+    const double theta4 = theta2 * theta2;
+    const double theta6 = theta4 * theta2;
+    const double theta8 = theta4 * theta4;
+    theta = thetad / (1.0 + c.k1 * theta2 + c.k2 * theta4 + c.k3 * theta6 + c.k4 * theta8);
+  }
+  const double scaling = tan(theta) / thetad;
+  x *= scaling;
+  y *= scaling;
+}
+
+SVOH_HD void atan_distort(const CamModelWide& c, double& x, double& y)
+{
+  const double r = sqrt(x * x + y * y);
+  const double factor = (r < 0.001) ? 1.0 : c.s_inv * atan(r * c.tans) / r;
+  x *= factor;
+  y *= factor;
+}
+
+SVOH_HD void atan_undistort(const CamModelWide& c, double& x, double& y)
+{
+  const double dist_r = sqrt(x * x + y * y);
+  const double r = tan(dist_r * c.k1) * c.tans_inv;
+  const double d_factor = (dist_r > 0.01) ? r / dist_r : 1.0;
+  x *= d_factor;
+  y *= d_factor;
+}
+
+SVOH_HD void project3(const CamModelWide& c, const Vec3& p, double& u, double& v)
+{
+  const double z_inv = 1 / p.z;
+  double x = p.x * z_inv, y = p.y * z_inv;
+  if (c.distortion == SVOH_DISTORTION_EQUIDISTANT) equidistant_distort(c, x, y);
+  else if (c.distortion == SVOH_DISTORTION_ATAN) atan_distort(c, x, y);
+  else if (c.distortion == SVOH_DISTORTION_RADTAN) radtan_distort(c, x, y);
+  u = c.fx * x + c.cx;
+  v = c.fy * y + c.cy;
+}
+
+// As project3_jacobian(CamModel): the narrow function for NONE | RADTAN.  ATAN has no Jacobian in the reference: every
+// entry refuses it on the host before a kernel could get here, and a Jacobian that slipped through anyway is NaN.
+SVOH_HD void project3_jacobian(const CamModelWide& c, const Vec3& p, double J[6])
+{
+  if (c.distortion != SVOH_DISTORTION_EQUIDISTANT && c.distortion != SVOH_DISTORTION_ATAN) {
+    project3_jacobian(static_cast<const CamModel&>(c), p, J);
+    return;
+  }
+  const double z_inv = 1 / p.z;
+  const double x = p.x * z_inv, y = p.y * z_inv;
+  const double d[6] = { z_inv, 0.0, -p.x * z_inv * z_inv, 0.0, z_inv, -p.y * z_inv * z_inv };
+  double J00 = NAN, J01 = NAN, J10 = NAN, J11 = NAN;
+  if (c.distortion == SVOH_DISTORTION_EQUIDISTANT) equidistant_jacobian(c, x, y, J00, J01, J10, J11);
+  for (int k = 0; k < 3; ++k) {
+    J[k] = c.fx * (J00 * d[k] + J01 * d[3 + k]);
+    J[3 + k] = c.fy * (J10 * d[k] + J11 * d[3 + k]);
+  }
+}
+
+SVOH_HD Vec3 back_project3(const CamModelWide& c, double u, double v)
+{
+  if (c.distortion != SVOH_DISTORTION_EQUIDISTANT && c.distortion != SVOH_DISTORTION_ATAN)
+    return back_project3(static_cast<const CamModel&>(c), u, v);
+  double x = (u - c.cx) * (1.0 / c.fx);
+  double y = (v - c.cy) * (1.0 / c.fy);
+  if (c.distortion == SVOH_DISTORTION_EQUIDISTANT) equidistant_undistort(c, x, y);
+  else atan_undistort(c, x, y);
+  Vec3 r = { x, y, 1.0 };
+  return r;
+}
+
+// does the reference evaluate AtanDistortion::jacobian (LOG(FATAL)) for this camera when a Jacobian is asked for?
+SVOH_HD bool camera_has_jacobian(const svoh_camera& c) { return c.distortion != SVOH_DISTORTION_ATAN; }
+SVOH_HD bool camera_is_narrow(const svoh_camera& c)
+{
+  return c.distortion == SVOH_DISTORTION_NONE || c.distortion == SVOH_DISTORTION_RADTAN;
+}
+SVOH_HD bool camera_is_known(const svoh_camera& c)
+{
+  return camera_is_narrow(c) || c.distortion == SVOH_DISTORTION_EQUIDISTANT || c.distortion == SVOH_DISTORTION_ATAN;
 }
 
 // ---- 8x8 LDL^T with diagonal pivoting (Eigen 3.4 LDLT<Lower> semantics) ----

@@ -31,13 +31,20 @@ def _camera(cam):
     c = capi.svoh_camera()
     c.fx, c.fy, c.cx, c.cy = cam.fx, cam.fy, cam.cx, cam.cy
     c.width, c.height = cam.width, cam.height
-    if cam.dist is None:
-        c.distortion = capi.SVOH_DISTORTION_NONE
-    else:
-        c.distortion = capi.SVOH_DISTORTION_RADTAN
-        for i in range(4):
-            c.d[i] = cam.dist[i]
+    model = getattr(cam, "model", None)
+    if model is None:   # a camera object without a model: radtan when it has coefficients, as before
+        model = "none" if cam.dist is None else "radtan"
+    if model not in _DISTORTION:
+        raise ValueError("unsupported camera model %r" % (model,))
+    c.distortion = _DISTORTION[model]
+    if model != "none":
+        for i, v in enumerate(cam.dist):
+            c.d[i] = v
     return c
+
+
+_DISTORTION = {"none": capi.SVOH_DISTORTION_NONE, "radtan": capi.SVOH_DISTORTION_RADTAN,
+               "equidistant": capi.SVOH_DISTORTION_EQUIDISTANT, "atan": capi.SVOH_DISTORTION_ATAN}
 
 
 def se3_to_numpy(s):
@@ -93,14 +100,15 @@ class Context(object):
         """The SVOH_* tuning knobs are read from the environment when the context is made; read them again."""
         self._check(self.lib.svoh_reload_knobs(self.h))
 
-    def camera_maths(self, cam, xyz):
-        """svoh_camera_maths: (px 2n, J 6n, f_back 3n) of the n points xyz (3n) as the DEVICE evaluates svoh_math.h."""
+    def camera_maths(self, cam, xyz, jacobian=True):
+        """svoh_camera_maths: (px 2n, J 6n, f_back 3n) of the n points xyz (3n) as the DEVICE evaluates svoh_math.h.
+        jacobian=False passes J = NULL (J is returned as None): the ATAN camera has no Jacobian."""
         xyz = np.ascontiguousarray(xyz, np.float64).ravel()
         n = xyz.size // 3
-        px, J, fb = np.zeros(2 * n), np.zeros(6 * n), np.zeros(3 * n)
+        px, J, fb = np.zeros(2 * n), (np.zeros(6 * n) if jacobian else None), np.zeros(3 * n)
         c = _camera(cam)
-        self._check(self.lib.svoh_camera_maths(self.h, C.byref(c), n, xyz.ctypes.data, px.ctypes.data, J.ctypes.data,
-                                               fb.ctypes.data))
+        self._check(self.lib.svoh_camera_maths(self.h, C.byref(c), n, xyz.ctypes.data, px.ctypes.data,
+                                               None if J is None else J.ctypes.data, fb.ctypes.data))
         return px, J, fb
 
     # ---- frames -----------------------------------------------------------

@@ -577,7 +577,7 @@ size_t FeatureTrackerHip::trackFrameBundle(const FrameBundle::Ptr& nframe_kp1)
     cur_frame->num_features_ = new_keypoints_counter;
     // frame_utils::computeNormalizedBearingVectors (frame.cpp:427-439)
     cur_frame->f_vec_.resize(3 * new_keypoints_counter);
-    const svoh::CamModel cm = svoh::load_camera(cur_frame->cam);
+    const svoh::CamModelWide cm = svoh::load_camera_wide(cur_frame->cam);
     for (size_t i = 0; i < new_keypoints_counter; ++i) {
       svoh::Vec3 f = svoh::back_project3(cm, new_keypoints[2 * i], new_keypoints[2 * i + 1]);
       const double nn = sqrt(f.x * f.x + f.y * f.y + f.z * f.z);
@@ -679,7 +679,7 @@ void DetectorHip::detect(const FramePtr& frame)
   frame->seed_ref_vec_.assign(frame->num_features_, Frame::SeedRef());
   frame->invmu_sigma2_a_b_vec_.resize(4 * frame->num_features_);
   frame->f_vec_.resize(3 * frame->num_features_);
-  const svoh::CamModel cm = svoh::load_camera(frame->cam);
+  const svoh::CamModelWide cm = svoh::load_camera_wide(frame->cam);
   for (size_t i = 0; i < frame->num_features_; ++i) {   // frame_utils::computeNormalizedBearingVectors
     const svoh::Vec3 f = svoh::back_project3(cm, px[2 * i], px[2 * i + 1]);
     const double nn = sqrt(f.x * f.x + f.y * f.y + f.z * f.z);
@@ -749,7 +749,7 @@ bool StereoTriangulationHip::prepare(const FramePtr& frame0, const FramePtr& fra
   f0.level_vec_.resize(n_old); f0.level_vec_.insert(f0.level_vec_.end(), new_levels.begin(), new_levels.end());
   f0.type_vec_.resize(n_old); f0.type_vec_.insert(f0.type_vec_.end(), new_types.begin(), new_types.end());
   f0.f_vec_.resize(3 * n0);
-  const svoh::CamModel cm0 = svoh::load_camera(f0.cam);
+  const svoh::CamModelWide cm0 = svoh::load_camera_wide(f0.cam);
   for (size_t i = n_old; i < n0; ++i) {   // frame_utils::computeNormalizedBearingVectors
     const svoh::Vec3 f = svoh::back_project3(cm0, f0.px_vec_[2 * i], f0.px_vec_[2 * i + 1]);
     const double nn = sqrt(f.x * f.x + f.y * f.y + f.z * f.z);
@@ -1059,7 +1059,7 @@ void appendSeeds(const FramePtr& frame, const std::vector<double>& px, const std
     else throw std::runtime_error("initializeSeeds: unknown feature type");   // LOG(FATAL)
   }
   frame->f_vec_.resize(3 * n);
-  const svoh::CamModel cm = svoh::load_camera(frame->cam);
+  const svoh::CamModelWide cm = svoh::load_camera_wide(frame->cam);
   for (size_t i = n_old; i < n; ++i) {
     const svoh::Vec3 f = svoh::back_project3(cm, frame->px_vec_[2 * i], frame->px_vec_[2 * i + 1]);
     const double nn = sqrt(f.x * f.x + f.y * f.y + f.z * f.z);
@@ -1145,7 +1145,7 @@ size_t Frame::numTrackedFeatures() const
 bool Frame::isVisible(const svoh::Vec3& xyz_w, double* px) const
 {
   const svoh::Vec3 xyz_f = svoh::transform(T_f_w_, xyz_w);
-  const svoh::CamModel cm = svoh::load_camera(cam);
+  const svoh::CamModelWide cm = svoh::load_camera_wide(cam);
   {   // pinhole: not farther off the optical axis than the image's top-left corner (frame.cpp:233-246)
     if (!min_cos_valid_ || memcmp(&min_cos_cam_, &cam, sizeof cam) != 0) {
       const svoh::Vec3 f_tl = svoh::back_project3(cm, 0.0, 0.0);

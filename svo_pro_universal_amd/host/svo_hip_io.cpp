@@ -285,6 +285,17 @@ std::vector<RigCamera> cameraRigFromYaml(const YamlNode& root)
       if (d.size() != 4) throw std::runtime_error("calibration: radial-tangential needs 4 parameters");
       for (int i = 0; i < 4; ++i) rc.cam.d[i] = d[i];
       rc.cam.distortion = SVOH_DISTORTION_RADTAN;
+    } else if (dtype == "equidistant") {   // PinholeEquidistantGeometry (camera_yaml_serialization.cpp:66-72)
+      const std::vector<double> d = dist["parameters"]["data"].asDoubles();
+      if (d.size() != 4) throw std::runtime_error("calibration: equidistant needs 4 parameters");
+      for (int i = 0; i < 4; ++i) rc.cam.d[i] = d[i];
+      rc.cam.distortion = SVOH_DISTORTION_EQUIDISTANT;
+    } else if (dtype == "fisheye") {       // PinholeAtanGeometry (:74-80): the FOV model, one parameter s
+      const std::vector<double> d = dist["parameters"]["data"].asDoubles();
+      if (d.size() != 1) throw std::runtime_error("calibration: fisheye needs 1 parameter");
+      if (!(d[0] != 0.0)) throw std::runtime_error("calibration: fisheye parameter s must be non-zero");
+      rc.cam.d[0] = d[0];
+      rc.cam.distortion = SVOH_DISTORTION_ATAN;
     } else if (dtype == "none" || dist.isNull()) {
       rc.cam.distortion = SVOH_DISTORTION_NONE;
     } else {
@@ -328,6 +339,7 @@ FrontendParams frontendParamsFromYaml(const YamlNode& node)
   p.depth_filter.seed_convergence_sigma2_thresh = node["seed_convergence_sigma2_thresh"].asDouble(200.0);
   p.depth_filter.mappoint_convergence_sigma2_thresh = node["mappoint_convergence_sigma2_thresh"].asDouble(500.0);
   p.depth_filter.scan_epi_unit_sphere = node["scan_epi_unit_sphere"].asBool(false);
+  p.poseoptim_using_unit_sphere = node["poseoptim_using_unit_sphere"].asBool(false);
   p.depth_filter.affine_est_offset = node["depth_filter_affine_est_offset"].asBool(true);
   p.depth_filter.affine_est_gain = node["depth_filter_affine_est_gain"].asBool(false);
   p.max_n_seeds_per_frame = (int)((double)node["max_fts"].asInt(120) * node["max_seeds_ratio"].asDouble(3.0));

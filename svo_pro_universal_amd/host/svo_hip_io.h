@@ -64,6 +64,7 @@ struct FrontendParams {
   FeatureTrackerOptions tracker;             // klt_* (svo_factory.cpp:305-306)
   int n_pyr_levels_to_build = 5;             // img_align_max_level + 1 (frame_handler_base.cpp:186)
   int structure_optimization_max_pts = 20;   // structure_optimization_max_pts (svo_factory.cpp:122)
+  bool poseoptim_using_unit_sphere = false;  // pose optimiser on bearing-vector differences (frame_handler_base.cpp:137-138)
 };
 FrontendParams frontendParamsFromYaml(const YamlNode& node);
 FrontendParams loadFrontendParams(const std::string& param_yaml_path);

@@ -92,7 +92,11 @@ struct FrontendLockstep::Stream {
 
   Stream(svoh_ctx* ctx, const LockstepOptions& o, const LockstepStreamOptions& own, const ReprojectorOptions& ropt)
       : so(own), img_align(ctx, SparseImgAlignHip::getDefaultSolverOptions(), own.params.img_align), reprojector(ctx, ropt, 0), pose_optimizer(ctx),
-        detector(ctx, own.params.detector, o.cam.width, o.cam.height) {}
+        detector(ctx, own.params.detector, o.cam.width, o.cam.height)
+  {
+    if (own.params.poseoptim_using_unit_sphere)   // frame_handler_base.cpp:137-138, as the single-stream harness
+      pose_optimizer.setErrorType(PoseOptimizerHip::ErrorType::kBearingVectorDiff);
+  }
 };
 
 void FrontendLockstep::check(int rc, const char* what) const
@@ -136,9 +140,10 @@ FrontendLockstep::FrontendLockstep(svoh_ctx* ctx, int n_streams, const LockstepO
         a.depth_filter.scan_epi_unit_sphere == b.depth_filter.scan_epi_unit_sphere && a.depth_filter.affine_est_offset == b.depth_filter.affine_est_offset &&
         a.depth_filter.affine_est_gain == b.depth_filter.affine_est_gain && a.detector.cell_size == b.detector.cell_size && a.detector.max_level == b.detector.max_level &&
         a.detector.min_level == b.detector.min_level && a.detector.border == b.detector.border && a.detector.detector_type == b.detector.detector_type &&
-        a.detector.threshold_primary == b.detector.threshold_primary && a.detector.threshold_secondary == b.detector.threshold_secondary;
+        a.detector.threshold_primary == b.detector.threshold_primary && a.detector.threshold_secondary == b.detector.threshold_secondary &&
+        a.poseoptim_using_unit_sphere == b.poseoptim_using_unit_sphere;   // one pose launch takes stream 0's residual type
     if (!same) throw std::runtime_error("FrontendLockstep: stream " + std::to_string(s) + " differs from stream 0 in an option that the streams' shared device calls take once "
-                                        "(pyramid levels, grid, detector, matcher / depth-filter switches): such streams belong in engines of their own");
+                                        "(pyramid levels, grid, detector, matcher / depth-filter switches, pose residual type): such streams belong in engines of their own");
     ReprojectorOptions ropt;
     ropt.max_n_features_per_frame = static_cast<size_t>(so.params.max_fts);
     ropt.cell_size = static_cast<size_t>(so.params.grid_size);

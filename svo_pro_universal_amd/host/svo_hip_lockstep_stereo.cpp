@@ -76,6 +76,8 @@ struct FrontendLockstepStereo::Stream {
         pose_optimizer(ctx), seed_detector(ctx, o.params.detector, o.rig[0].cam.width, o.rig[0].cam.height),
         tri_detector(new DetectorHip(ctx, o.params.detector, o.rig[0].cam.width, o.rig[0].cam.height)), stereo(ctx, triangulation_options(), tri_detector)
   {
+    if (o.params.poseoptim_using_unit_sphere)   // frame_handler_base.cpp:137-138, as the single-stream harness
+      pose_optimizer.setErrorType(PoseOptimizerHip::ErrorType::kBearingVectorDiff);
     rp[0] = &rp0; rp[1] = &rp1;
     rp0.sortPlannedListsOnly(true); rp1.sortPlannedListsOnly(true);
     stereo.shuffle_ = [this](std::vector<size_t>& idx, size_t n_corners) {

@@ -87,10 +87,24 @@ def se3_error(A, B):
 
 
 class Camera(object):
-    def __init__(self, width=640, height=480, fx=320.0, fy=320.0, cx=320.0, cy=240.0, dist=None):
+    """A pinhole camera.  model: None (today's behaviour: radtan when dist is given, else none), "radtan",
+    "equidistant" (dist = k1 k2 k3 k4, Kannala-Brandt) or "atan" (dist = [s], the FOV model of YAML type fisheye)."""
+
+    MODELS = ("none", "radtan", "equidistant", "atan")
+
+    def __init__(self, width=640, height=480, fx=320.0, fy=320.0, cx=320.0, cy=240.0, dist=None, model=None):
         self.width, self.height = int(width), int(height)
         self.fx, self.fy, self.cx, self.cy = float(fx), float(fy), float(cx), float(cy)
-        self.dist = None if dist is None else [float(x) for x in dist]  # k1 k2 p1 p2
+        self.dist = None if dist is None else [float(x) for x in dist]  # k1 k2 p1 p2 (radtan), k1..k4, or [s]
+        if model is None:
+            model = "none" if self.dist is None else "radtan"
+        if model not in self.MODELS:
+            raise ValueError("unknown camera model %r" % (model,))
+        if model != "none" and self.dist is None:
+            raise ValueError("camera model %r needs its parameters (dist)" % (model,))
+        if model == "atan" and len(self.dist) != 1 or model in ("radtan", "equidistant") and len(self.dist) != 4:
+            raise ValueError("camera model %r: wrong number of parameters %r" % (model, self.dist))
+        self.model = model
 
     @staticmethod
     def test_camera():
@@ -103,12 +117,28 @@ class Camera(object):
         return Camera(width, height, 458.654 * width / 752.0, 457.296, 367.215 * width / 752.0, 248.375,
                       dist=[-0.28340811, 0.07395907, 0.00019359, 1.76187114e-05])
 
+    @staticmethod
+    def visensor_like():
+        """The equidistant cam0 of examples/param/calib/visensor_flyingroom_mono.yaml (752x480)."""
+        return Camera(752, 480, 470.2057531638139, 470.6258233077641, 375.0680852766383, 224.00402741395007,
+                      dist=[0.004114762928023252, -0.028021075326115103, 0.12075408202580709, -0.10752125648784364],
+                      model="equidistant")
+
     # normalised, undistorted image-plane coordinates of pixel grids (xp arrays)
     def undistorted_xy(self, u, v):
         x = (u - self.cx) / self.fx
         y = (v - self.cy) / self.fy
-        if self.dist is None:
+        if self.model == "none":
             return x, y
+        if self.model == "equidistant":
+            return self._equidistant_inverse(x, y)
+        if self.model == "atan":
+            s = self.dist[0]
+            xp = _xp_of(x)
+            rd = (x * x + y * y) ** 0.5
+            r = xp.tan(rd * s) / (2.0 * math.tan(s / 2.0))
+            f = xp.where(rd > 0, r / xp.where(rd > 0, rd, 1.0), 1.0 / (2.0 * math.tan(s / 2.0)) * s)
+            return x * f, y * f
         k1, k2, p1, p2 = self.dist
         x0, y0 = x, y
         for _ in range(12):  # more iterations than the reference's 5: rendering wants the true inverse
@@ -121,18 +151,60 @@ class Camera(object):
             y = (y0 - dy) * ic
         return x, y
 
+    def _equidistant_inverse(self, x, y):
+        # theta_d = theta (1 + k1 theta^2 + ... + k4 theta^8) solved by Newton's method to convergence (the reference's
+        # five fixed-point iterations leave a residual that rendering should not carry), then r = tan(theta)
+        k1, k2, k3, k4 = self.dist
+        xp = _xp_of(x)
+        thetad = (x * x + y * y) ** 0.5
+        theta = thetad
+        for _ in range(20):
+            t2 = theta * theta
+            f = theta * (1.0 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4)))) - thetad
+            df = 1.0 + t2 * (3 * k1 + t2 * (5 * k2 + t2 * (7 * k3 + t2 * 9 * k4)))
+            theta = theta - f / df
+        pos = thetad > 0
+        scale = xp.where(pos, xp.tan(theta) / xp.where(pos, thetad, 1.0), 1.0)
+        return x * scale, y * scale
+
     def project(self, p):
         """numpy, p: 3xN -> 2xN (with distortion)."""
         x = p[0] / p[2]
         y = p[1] / p[2]
-        if self.dist is not None:
+        if self.model == "radtan":
             k1, k2, p1, p2 = self.dist
             xx, yy, xy = x * x, y * y, x * y
             r2 = xx + yy
             cd = (k1 + k2 * r2) * r2
             x, y = (x + x * cd + p1 * 2 * xy + p2 * (r2 + 2 * xx),
                     y + y * cd + p2 * 2 * xy + p1 * (r2 + 2 * yy))
+        elif self.model == "equidistant":
+            k1, k2, k3, k4 = self.dist
+            r = np.sqrt(x * x + y * y)
+            th = np.arctan(r)
+            t2 = th * th
+            thd = th * (1.0 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))))
+            sc = np.where(r < 1e-8, 1.0, thd / np.where(r > 0, r, 1.0))
+            x, y = x * sc, y * sc
+        elif self.model == "atan":
+            # the continuous FOV model (limit tans / s at the centre), the exact inverse of undistorted_xy.  The
+            # reference's distort() uses a factor of 1 below r = 0.001 instead: a step of a few per cent in scale
+            # within a pixel or so of the principal point, which the device maths and tests/np_restatement_cameras.py
+            # keep and a rendered scene does not
+            s = self.dist[0]
+            tans = 2.0 * math.tan(s / 2.0)
+            r = np.sqrt(x * x + y * y)
+            sc = np.where(r > 0, np.arctan(r * tans) / (s * np.where(r > 0, r, 1.0)), tans / s)
+            x, y = x * sc, y * sc
         return np.stack([self.fx * x + self.cx, self.fy * y + self.cy])
+
+
+def _xp_of(a):
+    """numpy or torch, by the array's type (render() runs on both)."""
+    if type(a).__module__.startswith("torch"):
+        import torch
+        return torch
+    return np
 
 
 # ----------------------------------------------------------------------------

@@ -165,6 +165,8 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
     ropt.affine_est_gain = params.reprojector_affine_est_gain;
     ReprojectorHip reprojector(ctx, ropt, 0);
     PoseOptimizerHip pose_optimizer(ctx);
+    if (params.poseoptim_using_unit_sphere)   // frame_handler_base.cpp:137-138
+      pose_optimizer.setErrorType(PoseOptimizerHip::ErrorType::kBearingVectorDiff);
     DepthFilterHip depth_filter(ctx, params.depth_filter);
     DetectorHip detector(ctx, params.detector, cam.width, cam.height);
 

@@ -303,6 +303,8 @@ int main(int argc, char** argv)
     ReprojectorHip reprojector0(ctx, ropt, 0), reprojector1(ctx, ropt, 1);
     ReprojectorHip* reprojectors[2] = { &reprojector0, &reprojector1 };
     PoseOptimizerHip pose_optimizer(ctx);
+    if (params.poseoptim_using_unit_sphere)   // frame_handler_base.cpp:137-138
+      pose_optimizer.setErrorType(PoseOptimizerHip::ErrorType::kBearingVectorDiff);
     DepthFilterHip depth_filter(ctx, params.depth_filter);
     DetectorHip seed_detector(ctx, params.detector, rig[0].cam.width, rig[0].cam.height);
     std::shared_ptr<DetectorHip> tri_detector(new DetectorHip(ctx, params.detector, rig[0].cam.width, rig[0].cam.height));
