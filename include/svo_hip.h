@@ -358,6 +358,15 @@ int svoh_sparse_align_last_kernel_ms(svoh_ctx* ctx, float* ms);
  * before one fetch.  *n_out = entries written. */
 int svoh_sparse_align_kernel_ms_history(svoh_ctx* ctx, int n, float* ms, int* n_out);
 
+/* Which kernel build the most recent FULL-RUN alignment launch on the context got (svoh_sparse_align_batch / _enqueue /
+ * _enqueue_keyed; not _evaluate, not the patch-split entries): the key of its launch geometry (the bits of
+ * svoh_sparse_align_geometry_key: workgroups per problem in bits 0-7, 512 threads in bit 8, lanes per patch in bits 9-12, the
+ * one-wave-per-SIMD build in bit 13, the side-by-side rig build in bit 14, bit 30 set), the number of workgroups launched and
+ * the number of problem descriptors they shared (problems x workgroups per problem).  Host-side bookkeeping of the enqueue
+ * call: valid as soon as it has returned, no synchronisation.  Fails before the first such launch.  For tests and tools
+ * that must KNOW which instantiation they measured instead of inferring it from the launch rule. */
+int svoh_sparse_align_last_launch_info(svoh_ctx* ctx, int32_t* geometry_key, int32_t* grid, int32_t* n_desc);
+
 /* Diagnostic/parity entry: evaluate H (8x8 col-major), g (8), chi2, n_meas for
  * ONE problem at a given level and state, i.e. SparseImgAlign::evaluateError
  * (sparse_img_align.cpp:115-156) on a fresh level.  visibility (may be NULL)

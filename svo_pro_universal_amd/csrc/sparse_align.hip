@@ -2294,7 +2294,8 @@ static AlignGeometry decide_geometry(const svoh_ctx* ctx, const svoh_align_optio
   g.nt = nt; g.rows = rows;
   // SVOH_ALIGN_LATENCY_BUILD=0 keeps the batch build for small launches too (A/B)
   g.latency = nt == 256 && !cluster && n_desc < ctx->num_cus && SvohKnobs::or_default(ctx->knobs.align_latency_build, 1) != 0;
-  g.rig = !cluster && n_desc < ctx->num_cus && z.have_rig;
+  // (the side-by-side build exists for the latency build and the 512-thread geometry only: launch_nt)
+  g.rig = !cluster && n_desc < ctx->num_cus && z.have_rig && (g.latency || nt == 512);
   return g;
 }
 
@@ -2672,6 +2673,9 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   if (timed) { SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_stop[ev_slot], ctx->stream)); ++ctx->align_timed_launches; }
   ctx->align_last_timed = timed;
   ++ctx->align_launches;
+  if (!split && eval_level < 0) {   // svoh_sparse_align_last_launch_info
+    ctx->align_last_geometry_key = geo.key(); ctx->align_last_grid = grid; ctx->align_last_n_desc = n_desc;
+  }
   // the results follow the kernel to pinned host memory right away, so that a caller which queues several
   // launches and fetches once still has every launch's output delivered
   if (delivers) {   // cluster: entry 0 is share 0's copy of the common result
@@ -2820,6 +2824,15 @@ try {
   const int slot = (int)((ctx->align_timed_launches - 1) % svoh_ctx::kAlignEventRing);
   SVOH_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_align_stop[slot]));
   SVOH_HIP_TRY(ctx, hipEventElapsedTime(ms, ctx->ev_align_start[slot], ctx->ev_align_stop[slot]));
+  return SVOH_OK;
+} SVOH_ABI_CATCH(ctx)
+
+int svoh_sparse_align_last_launch_info(svoh_ctx* ctx, int32_t* geometry_key, int32_t* grid, int32_t* n_desc)
+try {
+  if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  SVOH_REQUIRE(ctx, geometry_key && grid && n_desc, "NULL argument");
+  SVOH_REQUIRE(ctx, ctx->align_last_geometry_key != 0, "no full-run alignment launch on this context yet");
+  *geometry_key = ctx->align_last_geometry_key; *grid = ctx->align_last_grid; *n_desc = ctx->align_last_n_desc;
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
 

@@ -184,6 +184,15 @@ class Context(object):
         self._check(self.lib.svoh_sparse_align_fetch_all(self.h, n_total, res))
         return res
 
+    def last_align_launch(self):
+        """svoh_sparse_align_last_launch_info: which build the most recent full-run alignment launch got, decoded from its
+        geometry key -- dict(key, cluster_g, nt, rows, latency, rig, grid, n_desc)."""
+        key, grid, n_desc = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self.lib.svoh_sparse_align_last_launch_info(self.h, C.byref(key), C.byref(grid), C.byref(n_desc)))
+        k = key.value
+        return dict(key=k, cluster_g=k & 0xff, nt=512 if (k >> 8) & 1 else 256, rows=(k >> 9) & 0xf,
+                    latency=bool((k >> 13) & 1), rig=bool((k >> 14) & 1), grid=grid.value, n_desc=n_desc.value)
+
     def sparse_align_evaluate(self, opt, problem, level):
         H = np.zeros(64)
         g = np.zeros(8)

@@ -5,6 +5,11 @@ import numpy as np
 from svo_pro_universal_amd import _capi as capi, synth
 
 
+# the parity tolerances (tests/test_sparse_align_gpu.py explains them)
+TOL_HG = 1e-10
+TOL_POSE = 1e-8
+
+
 def scene_pyramids(orc, sc, n_levels=5, rounding=capi.SVOH_HALFSAMPLE_REFERENCE):
     return (orc.create_img_pyramid(sc.img_ref, n_levels, rounding),
             orc.create_img_pyramid(sc.img_cur, n_levels, rounding))
@@ -72,3 +77,29 @@ def se3_vec_diff(v, s):
     """golden 7-vector vs svoh_se3, quaternion-sign insensitive"""
     q = np.array([s.q[i] for i in range(4)]); t = np.array([s.t[i] for i in range(3)])
     return max(min(np.abs(v[:4] - q).max(), np.abs(v[:4] + q).max()), np.abs(v[4:] - t).max())
+
+
+def check_golden_fixtures(gpu_ctx, tag, after_run=None):
+    """HIP path vs the committed fixtures (no oracle call): H, g, visibility at every level and the full run of every option set of
+    GOLDEN_OPTION_SETS.  after_run(name): called behind each full run (a caller that forces a kernel build asserts there which one ran)."""
+    from svo_pro_universal_amd import frontend as fe
+    z = np.load(GOLDEN)
+    sc = scene_from_golden(z, tag)
+    fr, lv = gpu_ctx.build_pyramid(sc.img_ref, 4, return_levels=True)
+    fc, lvc = gpu_ctx.build_pyramid(sc.img_cur, 4, return_levels=True)
+    assert np.array_equal(lv[3], z[tag + "/ref_level3"]) and np.array_equal(lvc[3], z[tag + "/cur_level3"])
+    gpb, keep = fe.make_align_problems([[(sc, fr, fc)]])
+    for name, kw in GOLDEN_OPTION_SETS.items():
+        opt = capi.default_align_options(**kw)
+        q = "%s/%s/" % (tag, name)
+        for level in range(opt.min_level, opt.max_level + 1):
+            H, g, chi2, nm, vis = gpu_ctx.sparse_align_evaluate(opt, gpb[0], level)
+            assert np.array_equal(vis, z[q + "vis%d" % level]) and nm == int(z[q + "chi2_nmeas%d" % level][1])
+            assert np.abs(H - z[q + "H%d" % level]).max() <= TOL_HG * np.abs(H).max()
+            assert np.abs(g - z[q + "g%d" % level]).max() <= TOL_HG * np.abs(g).max()
+        res = gpu_ctx.sparse_align(opt, gpb)[0]
+        if after_run is not None:
+            after_run(name)
+        assert [res.n_fts_to_track, res.status, res.n_patch_iters] == list(z[q + "run_misc"])
+        assert list(res.iters) == list(z[q + "run_iters"]) and list(res.n_meas) == list(z[q + "run_nmeas"])
+        assert se3_vec_diff(z[q + "run_T"], res.T_icur_iref) < TOL_POSE

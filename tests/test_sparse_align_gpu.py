@@ -20,8 +20,8 @@ import helpers
 
 pytestmark = pytest.mark.gpu
 
-TOL_HG = 1e-10
-TOL_POSE = 1e-8
+TOL_HG = helpers.TOL_HG      # 1e-10
+TOL_POSE = helpers.TOL_POSE  # 1e-8
 
 
 def both(gpu_ctx, orc, scenes, n_levels=5, **mk):
@@ -259,24 +259,7 @@ def test_device_resident_inputs(gpu_ctx, oracle_lib):
 @pytest.mark.parametrize("tag", ["pinhole", "radtan"])
 def test_golden_fixtures(gpu_ctx, tag):
     """HIP path vs the committed fixtures (no oracle call)."""
-    z = np.load(helpers.GOLDEN)
-    sc = helpers.scene_from_golden(z, tag)
-    fr, lv = gpu_ctx.build_pyramid(sc.img_ref, 4, return_levels=True)
-    fc, lvc = gpu_ctx.build_pyramid(sc.img_cur, 4, return_levels=True)
-    assert np.array_equal(lv[3], z[tag + "/ref_level3"]) and np.array_equal(lvc[3], z[tag + "/cur_level3"])
-    gpb, keep = fe.make_align_problems([[(sc, fr, fc)]])
-    for name, kw in helpers.GOLDEN_OPTION_SETS.items():
-        opt = capi.default_align_options(**kw)
-        q = "%s/%s/" % (tag, name)
-        for level in range(opt.min_level, opt.max_level + 1):
-            H, g, chi2, nm, vis = gpu_ctx.sparse_align_evaluate(opt, gpb[0], level)
-            assert np.array_equal(vis, z[q + "vis%d" % level]) and nm == int(z[q + "chi2_nmeas%d" % level][1])
-            assert np.abs(H - z[q + "H%d" % level]).max() <= TOL_HG * np.abs(H).max()
-            assert np.abs(g - z[q + "g%d" % level]).max() <= TOL_HG * np.abs(g).max()
-        res = gpu_ctx.sparse_align(opt, gpb)[0]
-        assert [res.n_fts_to_track, res.status, res.n_patch_iters] == list(z[q + "run_misc"])
-        assert list(res.iters) == list(z[q + "run_iters"]) and list(res.n_meas) == list(z[q + "run_nmeas"])
-        assert helpers.se3_vec_diff(z[q + "run_T"], res.T_icur_iref) < TOL_POSE
+    helpers.check_golden_fixtures(gpu_ctx, tag)
 
 
 def test_full_size_properties(gpu_ctx):
