@@ -89,7 +89,8 @@ struct AlignKernelArgs {
   long long* stamps;                    // diagnostic builds only (SVOH_PHASE_STAMPS): 8 per problem
   int32_t n_problems;
   int32_t* queue;                       // work queue head: workgroups pull problem indices from it
-  int32_t one_each;                     // the grid has a workgroup per problem: workgroup b solves problem b, nobody asks the queue
+  int32_t one_each;                     // not read any more (the queue-less pull lost, see the kernel's pull); it stays because the layout of this block is part of
+                                        // every kernel's code: without it 72 functions change their instruction count and 29 kernels their scratch size
   // patch-split mode: evaluate at a caller-owned device state, hand out the undivided sums
   const svoh_align_gn_state* ext_state;
   int32_t raw_sums;
@@ -104,24 +105,6 @@ struct AlignKernelArgs {
 };
 
 constexpr int kXchgStride = 64;         // doubles per share and parity (>= 45 + 8 + 1 accumulators + 2)
-
-#ifndef SVOH_ROW_UNROLL_GONLY
-#define SVOH_ROW_UNROLL_GONLY 4
-#endif
-#ifndef SVOH_PIN_MOMENTS
-#define SVOH_PIN_MOMENTS 1
-#endif
-#ifndef SVOH_ALIGN_WAVE_STEP
-#define SVOH_ALIGN_WAVE_STEP 1
-#endif
-#ifndef SVOH_STEP_PRIO
-#define SVOH_STEP_PRIO 1
-#endif
-// rows of the full pass taken per loop trip: measured per configuration (round 3, scripts/ab.sh: 4x4 1.377 -> 1.365 ms with 2,
-// 1.44 with 4; 8x8 3.36 -> 3.25 with 4; with the illumination terms' 15 moments live, 1 for 4x4)
-#ifndef SVOH_ROW_UNROLL
-#define SVOH_ROW_UNROLL (PH == 8 ? 4 : (D == 8 ? 1 : 2))
-#endif
 
 #ifdef SVOH_PHASE_STAMPS
 // Diagnostic build only: wave 0 / lane 0 accumulates shader-clock cycles per
@@ -393,7 +376,9 @@ __device__ __forceinline__ void patch_moments_part(
   // next row's LDS / L2 reads overlap this row's arithmetic (1.64 -> 1.59 ms on the headline config)
   // (with Tukey weights a row carries a float division and the weighted forms of all moments: one row per trip -- four
   // unrolled rows of an 8x8 patch were 240-390 spilled registers)
-  constexpr int kRowUnroll = GONLY ? SVOH_ROW_UNROLL_GONLY : (ROB ? 1 : SVOH_ROW_UNROLL);
+  // rows of the full pass taken per loop trip: measured per configuration (round 3, scripts/ab.sh: 4x4 1.377 -> 1.365 ms with 2,
+  // 1.44 with 4; 8x8 3.36 -> 3.25 with 4; with the illumination terms' 15 moments live, 1 for 4x4)
+  constexpr int kRowUnroll = GONLY ? 4 : (ROB ? 1 : (PH == 8 ? 4 : (D == 8 ? 1 : 2)));
 #pragma unroll kRowUnroll
   for (int y = 0; y < PH; ++y) {
     const int rrow = roff + (y + 3) * ref.pitch;
@@ -614,13 +599,11 @@ __device__ __forceinline__ void stage_image(unsigned char* dst, const DevImage& 
   }
 }
 
-// SVOH_ALIGN_STAGE_REGS: a level's two images (reference and current) through registers instead of LDS-DMA -- every thread requests up to six
+// REGS: a level's two images (reference and current) through registers instead of LDS-DMA -- every thread requests up to six
 // 16-byte pieces of each image back to back (all in flight together), waits once and writes them to LDS.  Round 6, by the cycle stamps
 // (profiles/r06_align_p4_stamps.txt): the 50 KB of LDS-DMA requests of a problem's start take ~60 K cycles to arrive (a wave's global_load_lds
 // instructions return one behind the other), a fifth of the life of a 180-patch problem and 6 % of a 2000-patch one.
-#ifndef SVOH_ALIGN_STAGE_REGS
-#define SVOH_ALIGN_STAGE_REGS 1
-#endif
+// (LDS-DMA in the batch geometry too: lost; eight instead of four features requested together in the base phase: inside the spread -- profiles/r06_align_stage_regs_ab.txt)
 template <int NT, bool REGS>
 __device__ __forceinline__ void stage_image_pair(unsigned char* dst_a, const DevImage& im_a, unsigned char* dst_b, const DevImage& im_b, int tid)
 {
@@ -709,68 +692,13 @@ __device__ __forceinline__ Rigid uniform_rigid(const Rigid& T)
   return r;
 }
 
-// ---- what a pass over a camera's patches needs of the camera, per level -------------------------------------------------
-// The pass loop used to take it from the camera descriptor in global memory -- the two level images, the camera model,
-// the feature range: ~35 scalars through scalar loads whose addresses depend on the level -- in EVERY pass: 2.2 - 2.7 K
-// cycles per camera and pass by the cycle stamps (round 4), a fifth of a Gauss-Newton iteration of a 180-patch problem.
-// Now the level's start copies them into LDS once (LevelDesc, one thread per camera), and a pass reads them back uniformly
-// (ds_read + v_readfirstlane: values in scalar registers, as before).
-// MEASURED (round 5, A/B on one box, profiles/r05_align_desc_vote_ab.txt) AND NOT KEPT: a 180-patch problem 5.33 -> 5.68 us per
-// iteration with the descriptors in LDS alone, 5.38 - 5.42 with the vote folded as well; the batch of 1024 x 2000 within the
-// box's run-to-run spread (1.19 - 1.23 ms all three builds).  The scalar loads hit the scalar cache and overlap the
-// wave's other work; what the stamps attributed to them was the stamps' own s_waitcnt(0).  Both stay compiled out
-// (SVOH_ALIGN_LDS_DESC=1 / SVOH_ALIGN_FOLD_VOTE=1 build them: same results, all tests green).
-// SVOH_ALIGN_CLUSTER_XCD: the shares of a clustered problem placed on workgroups that share an XCD.  Built, measured
-// (profiles/r05_align_cluster_xcd_ab.txt), compiled out: up to 8 shares per problem nothing changes (2000 patches 0.154 against
-// 0.155 ms), with 16 - 32 shares one XCD is SLOWER than the eight the dispatcher spreads them over (8000 patches, 32 shares:
-// 0.334 against 0.266 ms; 20000: 0.352 against 0.279) -- the shares' image reads and workspace rows then go through one L2 and
-// one fabric port instead of eight, which costs more than the exchange slots meeting in one L2 saves (74 doubles per share and
-// iteration).
-#ifndef SVOH_ALIGN_CLUSTER_XCD
-#define SVOH_ALIGN_CLUSTER_XCD 0
-#endif
-// SVOH_ALIGN_ONE_EACH: launches whose grid has a workgroup per problem skip the work queue.  Built, measured
-// (profiles/r05_align_one_each_ab.txt: one 180-patch problem 5.35 us per iteration + 27.1 us either way), compiled out: the
-// returning atomic on the queue head is not what a lone problem's launch pays for.
-#ifndef SVOH_ALIGN_ONE_EACH
-#define SVOH_ALIGN_ONE_EACH 0
-#endif
-#ifndef SVOH_ALIGN_LDS_DESC
-#define SVOH_ALIGN_LDS_DESC 0
-#endif
-// ... and the visibility vote of a gradient-only pass rides the reduction's barrier instead of having one of its own
-#ifndef SVOH_ALIGN_FOLD_VOTE
-#define SVOH_ALIGN_FOLD_VOTE 0
-#endif
-struct LevelDesc {
-  DevImage ref, cur;
-  svoh_camera cam;
-  int32_t n_features, feat_off;
-};
+// ---- what a pass over a camera's patches needs of the camera ------------------------------------------------------------
+// Taken from the camera descriptor in global memory by scalar loads, in every pass.  (Copied into LDS once per level instead: tried,
+// lost -- HISTORY.md round 5, "Alignment kernel: two of the items ...", profiles/r05_align_desc_vote_ab.txt)
 struct CamPass {   // the uniform copy a pass works with
   svoh_camera cam;
   int32_t n_features, feat_off;
 };
-__device__ __forceinline__ int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ DevImage uniform_image(const DevImage& im)
-{
-  DevImage r;
-  const unsigned long long p = reinterpret_cast<unsigned long long>(im.data);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)p), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32));
-  r.data = reinterpret_cast<const uint8_t*>(((unsigned long long)hi << 32) | lo);
-  r.w = uniform_i32(im.w); r.h = uniform_i32(im.h); r.pitch = uniform_i32(im.pitch); r.pad = 0;
-  return r;
-}
-__device__ __forceinline__ CamPass uniform_cam_pass(const LevelDesc& d)
-{
-  CamPass r;
-  r.cam.fx = uniform_f64(d.cam.fx); r.cam.fy = uniform_f64(d.cam.fy); r.cam.cx = uniform_f64(d.cam.cx); r.cam.cy = uniform_f64(d.cam.cy);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) r.cam.d[k] = uniform_f64(d.cam.d[k]);
-  r.cam.distortion = uniform_i32(d.cam.distortion); r.cam.width = uniform_i32(d.cam.width); r.cam.height = uniform_i32(d.cam.height); r.cam.reserved = 0;
-  r.n_features = uniform_i32(d.n_features); r.feat_off = uniform_i32(d.feat_off);
-  return r;
-}
 
 constexpr int kWsPairs = 3;
 __device__ __forceinline__ double* ws_pair(const AlignKernelArgs& a, int pair, int64_t gi) { return a.wpk + ((int64_t)pair * a.slots + gi) * 2; }
@@ -845,7 +773,6 @@ __device__ __forceinline__ void accumulate_camera(
     double mom[AccLayout<D>::NMOM];
     patch_moments<P, D, LDS, LDS, GONLY, ROB>(ref, cur, ru, rv, rsu, rsv, cu, cv, csu, csv, one_plus_alpha, beta_d, robust,
                                               weight_scale, mom);
-#if SVOH_PIN_MOMENTS
     // see accumulate_camera_rows: the moments are finished here, the pixel arithmetic is not sunk behind what follows.
     // On the LDS-resident levels only: where the rows come from global memory the interleaving hides their latency
     // (A/B on one box, 1024 x 2000 patches: levels 4..2 0.996 -> 0.904-0.954 ms with the pin, level 0 alone 0.787 -> 0.82-0.84)
@@ -854,7 +781,6 @@ __device__ __forceinline__ void accumulate_camera(
       for (int k = 0; k < AccLayout<D>::NMOM; ++k)
         if (!GONLY || k == 3 || k == 4 || k == 5 || k == 13 || k == 14) asm volatile("" : "+v"(mom[k]));
     }
-#endif
     SVOH_PASS_STAMP(3);
     double ja[6], jb[6];
     jac_rows(jc, cm, dist_jac, X, scale, ja, jb);
@@ -1023,13 +949,11 @@ __device__ __forceinline__ void accumulate_camera_staged(
       }
     }
     if (vis) {
-#if SVOH_PIN_MOMENTS
       if constexpr (LDS) {   // see accumulate_camera
 #pragma unroll
         for (int k = 0; k < AccLayout<D>::NMOM; ++k)
           if (!GONLY || k == 3 || k == 4 || k == 5 || k == 13 || k == 14) asm volatile("" : "+v"(mom[k]));
       }
-#endif
 
       asm volatile("" ::: "memory");   // xyz_ref comes from LDS again here instead of living through the pixel loop
       const double2 xy2 = *reinterpret_cast<const double2*>(buf + 0 * 128 + lane * 2);
@@ -1406,20 +1330,6 @@ __device__ __attribute__((noinline)) void gn_wave_step(const AlignKernelArgs& a,
   SVOH_WAVE_STAMP(3);
 }
 
-#ifndef SVOH_ALIGN_STAGED
-#define SVOH_ALIGN_STAGED 1
-#endif
-#ifndef SVOH_ALIGN_REUSE_HESSIAN
-#define SVOH_ALIGN_REUSE_HESSIAN 1
-#endif
-#ifndef SVOH_ALIGN_MIN_WAVES_256
-#define SVOH_ALIGN_MIN_WAVES_256 2
-#endif
-// the lanes per patch a small problem gets by default, as a function of what fits (measured: DESIGN.md 4.2)
-#ifndef SVOH_ALIGN_ROWS_DEFAULT
-#define SVOH_ALIGN_ROWS_DEFAULT(fit) (fit)
-#endif
-
 // CLUSTER: the cluster mode's exchanges are compiled in (256-thread geometry only); the batch instantiation stays
 // free of them -- as run-time branches they cost the batch kernel 5 %.
 // ROBUST: the Tukey weights (SparseImgAlignOptions::robustification, off in the reference's handlers) as a compile-time
@@ -1437,7 +1347,7 @@ __device__ __attribute__((noinline)) void gn_wave_step(const AlignKernelArgs& a,
 // single-camera problem 1.5 - 4 % of its kernel (measured: register allocation and a scalar-load dependency per pass),
 // which the mono chain should not pay.
 template <int P, int NT, bool ILLUM, bool CLUSTER = false, bool ROBUST = false, int LPP = 1, bool LAT = false, bool RIG = false>
-__global__ __launch_bounds__(NT, (NT == 256 ? (LAT ? 1 : SVOH_ALIGN_MIN_WAVES_256) : 2))
+__global__ __launch_bounds__(NT, (NT == 256 ? (LAT ? 1 : 2) : 2))   // 256 threads: two workgroups per compute unit (256 registers), the latency build one
 void sparse_align_kernel(const AlignKernelArgs a)
 {
   static_assert(!LAT || (NT == 256 && !CLUSTER && LPP == 1), "latency build: the 256-thread lane-per-patch geometry");
@@ -1451,11 +1361,11 @@ void sparse_align_kernel(const AlignKernelArgs a)
 
   // LDS-DMA staging of the workspace rows (accumulate_camera_staged) in the batch geometry; the wide
   // geometries keep their LDS for finer image levels and read the workspace with ordinary loads
-  constexpr bool STAGED = SVOH_ALIGN_STAGED && NT == 256 && !ROWS;
+  constexpr bool STAGED = NT == 256 && !ROWS;
   // the levels' images through registers in the BATCH geometry only (stage_item_list): a workgroup there has a second one beside it on its compute
   // unit to fill the wait; the small-launch geometries keep the LDS-DMA requests, whose flight overlaps the problem's base phase (measured, one
   // 180-patch problem: 27.6 us outside the iterations with LDS-DMA, 31.3 with the blocking copy)
-  constexpr bool kStageRegs = SVOH_ALIGN_STAGE_REGS != 0 && NT == 256 && !LAT && !CLUSTER && !ROWS;
+  constexpr bool kStageRegs = NT == 256 && !LAT && !CLUSTER && !ROWS;
   extern __shared__ __align__(16) unsigned char lds_img[];
   __shared__ __align__(16) double s_stage[STAGED ? NW * kStageDoubles : 2];
   __shared__ double s_jc[SVOH_MAX_CAMS][kJacConsts];   // per-camera constants of jac_rows
@@ -1464,8 +1374,6 @@ void sparse_align_kernel(const AlignKernelArgs a)
   static_assert(NACC <= 45, "g_sum is sized for the 8-parameter case");
   __shared__ double s_x[kXchgStride];   // cluster mode: the block handed to cluster_sum
   __shared__ int s_cluster_ok;
-  [[maybe_unused]] __shared__ __align__(16) LevelDesc s_lvd[SVOH_ALIGN_LDS_DESC ? SVOH_MAX_CAMS : 1];   // the cameras at the current level (see LevelDesc)
-  [[maybe_unused]] __shared__ int s_changed[SVOH_ALIGN_FOLD_VOTE ? NW : 1];   // a gradient-only pass' visibility vote, wave by wave (SVOH_ALIGN_FOLD_VOTE)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -1474,40 +1382,10 @@ void sparse_align_kernel(const AlignKernelArgs a)
   // Persistent workgroups: the grid is sized to what is resident at once and every
   // workgroup pulls the next problem index from a queue head, so problems that need
   // more Gauss-Newton iterations do not leave CUs idle at the end of the launch.
-#if SVOH_ALIGN_CLUSTER_XCD
-  bool first_pull = true;
-#endif
-#if SVOH_ALIGN_ONE_EACH
-  bool pulled_once = false;
-#endif
+  // (a clustered problem's shares placed on one XCD by block index, and the problem index taken from the block index when the grid
+  // has a workgroup per problem: both tried, both lost -- HISTORY.md round 5, profiles/r05_align_cluster_xcd_ab.txt, r05_align_one_each_ab.txt)
   for (;;) {
   __syncthreads();  // everyone is done with the previous problem's shared state
-#if SVOH_ALIGN_CLUSTER_XCD
-  // Cluster mode: a workgroup takes exactly one share, and WHICH one follows from its block index -- the shares of a problem go
-  // to blocks b, b + 8, b + 16, ..., which the dispatcher is observed to deal to ONE XCD (round robin over the eight: a label
-  // for speed, never for correctness): the shares' exchange slots and the images they all read then meet in one L2.  The
-  // launch's grid is 8 x cluster x ceil(problems / 8) blocks; blocks beyond the last problem leave at once.
-  if constexpr (CLUSTER) {
-    if (tid == 0) {
-      int v = a.n_problems;
-      if (first_pull) {
-        const int x = (int)(blockIdx.x & 7u), srow = (int)(blockIdx.x >> 3);
-        const int c = x + 8 * (srow / a.cluster);
-        if (c < a.n_problems / a.cluster) v = c * a.cluster + srow % a.cluster;
-      }
-      s_pbi = v;
-    }
-    first_pull = false;
-  } else
-#endif
-#if SVOH_ALIGN_ONE_EACH
-  // a launch with a workgroup per problem (one problem alone, a camera stream's frame, the problems of a lock-step round): the
-  // problem index is the block index -- no returning atomic on the queue head ahead of the first descriptor load
-  if (a.one_each) {
-    if (tid == 0) s_pbi = pulled_once ? a.n_problems : (int)blockIdx.x;
-    pulled_once = true;
-  } else
-#endif
   if (tid == 0) s_pbi = atomicAdd(a.queue, 1);
   __syncthreads();
   const int pbi = s_pbi;
@@ -1590,11 +1468,6 @@ void sparse_align_kernel(const AlignKernelArgs a)
       stage_item_list<NT>(lds_img, s_stage_items, n_items, total16, tid);
     }
   }
-#ifdef SVOH_STAGE_WAIT_EXPERIMENT
-  // diagnostic build only (with SVOH_PHASE_STAMPS): wait for the levels' LDS-DMA right here and book it as "stage" -- how long the 50 KB take by themselves
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  SVOH_STAMP_ADD(1);
-#endif
   if (tid == 0) {
     g_state.T = load_rigid(pb.T_init);
     g_state.Told = g_state.T;
@@ -1660,10 +1533,7 @@ void sparse_align_kernel(const AlignKernelArgs a)
       // (65 bytes per feature, read once), and the vector-memory counter is in order -- with one feature requested ahead
       // every trip waited for the PREVIOUS trip's stores as well (round 4 stamps: 99 K cycles per 2000-feature problem,
       // 12 K per trip: 9 % of a workgroup's life in the batch)
-#ifndef SVOH_ALIGN_BASE_DEPTH
-#define SVOH_ALIGN_BASE_DEPTH 4
-#endif
-      constexpr int kBaseDepth = SVOH_ALIGN_BASE_DEPTH;
+      constexpr int kBaseDepth = 4;
       for (int i0 = tid; i0 < cd.n_features; i0 += kBaseDepth * NT) {
         FeatIn in[kBaseDepth];
 #pragma unroll
@@ -1770,13 +1640,6 @@ void sparse_align_kernel(const AlignKernelArgs a)
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this thread's image requests (issued here or at the problem's start) have landed
     __syncthreads();
-#if SVOH_ALIGN_LDS_DESC
-    if (tid >= 64 && tid < 64 + n_cams) {   // (a lane of the second wave per camera: the first wave's lane 0 is busy below)
-      const DevCamDesc& cdg = cams[tid - 64];
-      LevelDesc& ld = s_lvd[tid - 64];
-      ld.ref = cdg.ref[level]; ld.cur = cdg.cur[level]; ld.cam = cdg.cam; ld.n_features = cdg.n_features; ld.feat_off = cdg.feat_off;
-    }
-#endif
     if (tid == 0) {
       g_state.level_done = 0;
       for (int c = 0; c < n_cams; ++c)
@@ -1795,7 +1658,7 @@ void sparse_align_kernel(const AlignKernelArgs a)
       // the gradient and chi2 only and the solver reuses the level's factorisation.  A pass that finds a patch
       // whose visibility differs from the last full pass is thrown away and repeated in full: the numbers are
       // those of recomputing the Hessian every iteration, as the reference does.
-      bool light = SVOH_ALIGN_REUSE_HESSIAN && !eval_mode && !robust && iter > 0;
+      bool light = !eval_mode && !robust && iter > 0;
       for (;;) {
         int nvis = 0, changed = 0;
         auto run_cameras = [&](auto gonly_tag, auto& acc_ref) {
@@ -1810,17 +1673,11 @@ void sparse_align_kernel(const AlignKernelArgs a)
           // (side_by_side: decided once per problem, above the level loop)
           int cam_base = 0;
           for (int c = 0; c < n_cams; ++c) {
-#if SVOH_ALIGN_LDS_DESC
-            const CamPass cd = uniform_cam_pass(s_lvd[c]);
-            const DevImage rim = uniform_image(s_lvd[c].ref);
-            const DevImage cim = uniform_image(s_lvd[c].cur);
-#else
             const DevCamDesc& cdg = cams[c];
             CamPass cd;
             cd.cam = cdg.cam; cd.n_features = cdg.n_features; cd.feat_off = cdg.feat_off;
             const DevImage& rim = cdg.ref[level];
             const DevImage& cim = cdg.cur[level];
-#endif
             const Rigid Tcr = uniform_rigid(g_state.Tcr[c]);
             unsigned cam_stride = NT, cam_t = (unsigned)tid;
             if (RIG && side_by_side) {   // (uniform)
@@ -1879,37 +1736,7 @@ void sparse_align_kernel(const AlignKernelArgs a)
           SVOH_OUTER_STAMP_BEGIN();
           run_cameras(std::true_type(), accg);
           SVOH_OUTER_STAMP(5);   // includes the pieces 0..4 counted inside
-#if SVOH_ALIGN_FOLD_VOTE
-          // The vote -- did any patch's visibility differ from the last full pass? -- travels with the reduction: every wave
-          // leaves its own verdict in LDS next to its partial sums, ONE barrier, and everybody reads the NW verdicts.  A pass
-          // that is thrown away has reduced for nothing (that is rare: none on the benchmark scenes); every other pass has one
-          // barrier less (1.1 K cycles of a 180-patch problem's iteration by the stamps).  nvis is only added once the pass counts.
-          {
-            int ridx;
-            bool rvalid;
-            wave_reduce_scatter<D + 1>(accg, lane, ridx, rvalid);
-            if (rvalid) s_red[wave][ridx] = accg[0];
-          }
-          {
-            const int wave_changed = __builtin_amdgcn_ballot_w64(changed != 0) != 0ull;
-            if (lane == 0) s_changed[wave] = wave_changed;
-          }
-          nvis = wave_sum_i32_dpp(nvis);
-          __syncthreads();
-          int changed_here = 0;
-#pragma unroll
-          for (int w = 0; w < NW; ++w) changed_here |= s_changed[w];
-          SVOH_OUTER_STAMP(6);
-          if (changed_here && !cluster) {   // visibility moved: this iteration in full
-            SVOH_STAMP_COUNT(5);
-            light = false;
-            __syncthreads();   // (everybody has read the verdicts and nobody reads this pass' partial sums: the full pass may write both)
-            continue;
-          }
-          SVOH_STAMP_COUNT(6);
-          SVOH_STAMP_ADD(2);
-          if (lane == 0) atomicAdd(&g_nvis, nvis);
-#else
+          // (the vote carried by the reduction's barrier, one barrier less: tried, lost -- HISTORY.md round 5, profiles/r05_align_desc_vote_ab.txt)
           const int changed_here = __syncthreads_or(changed);
           SVOH_OUTER_STAMP(6);
           if (changed_here && !cluster) {   // visibility moved: this iteration in full
@@ -1928,7 +1755,6 @@ void sparse_align_kernel(const AlignKernelArgs a)
           nvis = wave_sum_i32_dpp(nvis);
           if (lane == 0) atomicAdd(&g_nvis, nvis);
           __syncthreads();
-#endif
           if (tid < D + 1) {   // gradient and chi2 only: g_sum[0 .. NH) still holds the level's Hessian
             double v = 0.0;
             for (int w = 0; w < NW; ++w) v += s_red[w][tid];
@@ -1990,22 +1816,14 @@ void sparse_align_kernel(const AlignKernelArgs a)
 
       SVOH_STAMP_ADD(3);
       // ---- serial part: prior, pivoted LDL^T (or the level's factor again), SE3 update, convergence ----
-#if SVOH_ALIGN_WAVE_STEP
       if (eval_mode) { if (tid == 0) gn_serial_step<P, D, ILLUM>(a, pb, cams, n_cams, res_idx, level, iter, eval_mode, light); }
       else if (tid < 64) {
         // the step is its workgroup's critical path (three waves wait at the barrier behind it): it goes ahead of the
         // other workgroup's pass waves on its SIMD
-#if SVOH_STEP_PRIO
         __builtin_amdgcn_s_setprio(3);
-#endif
         gn_wave_step<P, D, ILLUM>(a, n_cams, level, iter, light, tid);
-#if SVOH_STEP_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
       }
-#else
-      if (tid == 0) gn_serial_step<P, D, ILLUM>(a, pb, cams, n_cams, res_idx, level, iter, eval_mode, light);
-#endif
       __syncthreads();
       SVOH_STAMP_ADD(4);
       if (g_state.level_done) break;
@@ -2281,7 +2099,6 @@ static AlignGeometry decide_geometry(const svoh_ctx* ctx, const svoh_align_optio
   int rows = 1;
   if (!cluster && n_desc < ctx->num_cus) {
     while (rows * 2 <= opt->patch_size && rows * 2 <= 8 && (int64_t)z.max_feat_per_problem * rows * 2 <= 256) rows *= 2;
-    rows = SVOH_ALIGN_ROWS_DEFAULT(rows);
   }
   rows = SvohKnobs::or_default(ctx->knobs.align_rows, rows);
   if (rows != 2 && rows != 4 && rows != 8) rows = 1;
@@ -2625,7 +2442,7 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   args.lds_two_per_cu = (nt == 256 && !cluster && ctx->knobs.align_lds == kKnobUnset && ctx->knobs.align_wg_per_cu == kKnobUnset) ? 1 : 0;
   lds = (size_t)SvohKnobs::or_default(ctx->knobs.align_lds, (int)lds) & ~(size_t)15;   // the workspace behind the image area is read through 16-byte loads
   // 160 KB per workgroup minus the kernel's static LDS
-  const size_t lds_cap = (nt == 256 && SVOH_ALIGN_STAGED) ? 163840 - 32768 : 153856;
+  const size_t lds_cap = (nt == 256) ? 163840 - 32768 : 153856;
   if (lds > lds_cap) lds = lds_cap;
   // a small problem's feature workspace in LDS, behind the image area (512-thread geometry: 78 KB hold the 50 KB of the
   // levels 4..2 of a 640x480 pair and 16 KB of rows; the next finer level would not fit either way)
@@ -2640,10 +2457,7 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   int grid = ctx->num_cus * SvohKnobs::or_default(ctx->knobs.align_wg_per_cu, nt == 256 ? 2 : 1);
   if (grid > n_desc || grid <= 0) grid = n_desc;
   if (cluster) grid = n_desc;
-  args.one_each = (!cluster && grid == n_desc) ? 1 : 0;
-#if SVOH_ALIGN_CLUSTER_XCD
-  if (cluster) grid = 8 * args.cluster * ((n_desc / args.cluster + 7) / 8);   // (see the kernel's pull)
-#endif
+  args.one_each = 0;   // (not read: see AlignKernelArgs)
   hipError_t e;
   const bool timed = ctx->timing_on();
   const int ev_slot = (int)(ctx->align_timed_launches % svoh_ctx::kAlignEventRing);
