@@ -864,10 +864,10 @@ int svoh_detect_features(svoh_ctx* ctx, svoh_frame_t frame, const svoh_detector_
  * half: for every frame and grid cell the best corner (key: score << 32 | ~(level, y, x), as fd_utils::fastDetector's
  * per-cell best, 0 = none above threshold_primary) and, in the cells that neither `occupancy` nor a corner takes, the
  * best edgelet (key: float bits of the magnitude << 32 | ~(y, x) on level 1) with its histogram angle.  occupancy: n_frames
- * x n_cells bytes or NULL; the three outputs n_frames x n_cells each (host).  No mask (a masked-out corner would have to
- * free its cell between the two phases).  svoh_detect_fill_features is the host half, fd_utils::fillFeatures for corners
+ * x n_cells bytes or NULL; the three outputs n_frames x n_cells each (host).  Frames with a camera mask go through
+ * svoh_detect_cells_batch_masked below.  svoh_detect_fill_features is the host half, fd_utils::fillFeatures for corners
  * then edgelets of ONE frame from its n_cells entries of each array: pure host code without a context, callable from
- * any thread.  Both halves together give exactly svoh_detect_features' features (mask == NULL). */
+ * any thread.  Both halves together give exactly svoh_detect_features' features (mask == NULL here). */
 int svoh_detect_cells_batch(svoh_ctx* ctx, int n_frames, const svoh_frame_t* frames, const svoh_detector_options* options,
                             const uint8_t* occupancy, uint64_t* corner_keys, uint64_t* edge_keys, float* edge_angles);
 /* The device half in two steps: _enqueue queues uploads, kernels and the copy of the results and returns; _collect waits for
@@ -880,6 +880,28 @@ int svoh_detect_cells_batch_collect(svoh_ctx* ctx, uint64_t* corner_keys, uint64
 int svoh_detect_fill_features(const svoh_detector_options* options, int width, int height, const uint64_t* corner_keys,
                               const uint64_t* edge_keys, const float* edge_angles, int max_n_features, double* px,
                               double* score, int32_t* level, double* grad, uint8_t* type, int32_t* n_features);
+
+/* A camera's mask resident on the device: a level-0 sized u8 image, 0 = never a feature here (the mask image a calibration
+ * file names; camera_geometry_base.cpp:62-76).  Uploaded once per camera, not per frame.  pitch: bytes between rows (>= width).
+ * 0 is never a valid handle: it stands for "no mask".  svoh_mask_release waits for the device (kernels queued before it may
+ * still read the mask); an unknown or released handle is SVOH_ERR_BAD_HANDLE.  svoh_destroy releases what is left.
+ * (svoh_context_stats does not count masks: its struct has no field to spare.) */
+typedef uint64_t svoh_mask_t;
+int svoh_mask_upload(svoh_ctx* ctx, int width, int height, int pitch, const uint8_t* data, svoh_mask_t* out_mask);
+int svoh_mask_release(svoh_ctx* ctx, svoh_mask_t mask);
+
+/* svoh_detect_cells_batch / _enqueue with a mask per frame: masks holds n_frames handles (0 = this frame has none) or is NULL
+ * (no frame has one: exactly the unmasked entries, the same kernels).  A mask must have the size of the frames' level 0
+ * (SVOH_ERR_INVALID_ARGUMENT otherwise).  The mask acts BETWEEN the phases, as fillFeatures does in the reference
+ * (feature_detection.cpp:157-194): a cell whose best corner lies on a zero mask pixel loses its key and is free for the
+ * edgelet phase; an edgelet winner on a zero pixel is cleared too (before its angle is computed).  A cleared winner is not
+ * replaced by the cell's second best.  svoh_detect_cells_batch_collect serves both kinds of batch, and svoh_detect_fill_features
+ * of a frame's arrays gives exactly svoh_detect_features' features for the same frame, options, occupancy and mask. */
+int svoh_detect_cells_batch_masked(svoh_ctx* ctx, int n_frames, const svoh_frame_t* frames, const svoh_detector_options* options,
+                                   const uint8_t* occupancy, const svoh_mask_t* masks, uint64_t* corner_keys, uint64_t* edge_keys,
+                                   float* edge_angles);
+int svoh_detect_cells_batch_masked_enqueue(svoh_ctx* ctx, int n_frames, const svoh_frame_t* frames, const svoh_detector_options* options,
+                                           const uint8_t* occupancy, const svoh_mask_t* masks);
 
 /* feature_detection_utils::getAngleAtPixelUsingHistogram(img_pyr[level], px, 4) (feature_detection_utils.cpp:831-839, 947-1009) for n
  * pixels of possibly different frames and levels in one call: bins[k] = the dominant bin (0 .. 35) of the smoothed 36-bin histogram of the

@@ -31,6 +31,7 @@ SVOH_HALFSAMPLE_SCALAR = 1
 SVOH_HALFSAMPLE_SSE2 = 2
 
 svoh_frame_t = C.c_uint64
+svoh_mask_t = C.c_uint64   # 0 = no mask
 
 
 class svoh_se3(C.Structure):
@@ -306,6 +307,8 @@ EXPORTS = [
     "svoh_sparse_align_geometry_key", "svoh_sparse_align_enqueue_keyed",
     "svoh_project_candidates_stage", "svoh_project_candidates_stage_ranges", "svoh_project_candidates_enqueue_staged", "svoh_project_candidates_enqueue_staged_units", "svoh_project_candidates_wait",
     "svoh_matcher_stage", "svoh_detect_cells_batch", "svoh_detect_cells_batch_enqueue", "svoh_detect_cells_batch_collect", "svoh_detect_fill_features", "svoh_histogram_angle_bins", "svoh_features_upload", "svoh_features_release", "svoh_select_matches_batch",
+    # camera masks: resident on the device, applied between the two phases of the batched detector
+    "svoh_mask_upload", "svoh_mask_release", "svoh_detect_cells_batch_masked", "svoh_detect_cells_batch_masked_enqueue",
 ]
 
 
@@ -445,6 +448,10 @@ def load(path=None):
     lib.svoh_detect_cells_batch.argtypes = [C.c_void_p, C.c_int, P(svoh_frame_t), P(svoh_detector_options), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.svoh_detect_cells_batch_enqueue.argtypes = [C.c_void_p, C.c_int, P(svoh_frame_t), P(svoh_detector_options), C.c_void_p]
     lib.svoh_detect_cells_batch_collect.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.svoh_mask_upload.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, P(svoh_mask_t)]
+    lib.svoh_mask_release.argtypes = [C.c_void_p, svoh_mask_t]
+    lib.svoh_detect_cells_batch_masked.argtypes = [C.c_void_p, C.c_int, P(svoh_frame_t), P(svoh_detector_options), C.c_void_p, P(svoh_mask_t), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.svoh_detect_cells_batch_masked_enqueue.argtypes = [C.c_void_p, C.c_int, P(svoh_frame_t), P(svoh_detector_options), C.c_void_p, P(svoh_mask_t)]
     lib.svoh_histogram_angle_bins.argtypes = [C.c_void_p, C.c_int, P(svoh_frame_t), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.svoh_detect_fill_features.argtypes = [P(svoh_detector_options), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int32)]

@@ -534,6 +534,8 @@ try {
   if (ctx->stream) { (void)hipStreamSynchronize(ctx->stream); }
   if (ctx->upload_stream) { (void)hipStreamSynchronize(ctx->upload_stream); }
   ctx->frames.clear();
+  for (auto& kv : ctx->masks) (void)hipFree(kv.second.ptr);
+  ctx->masks.clear();
   for (int k = 0; k < svoh_ctx::kAlignEventRing; ++k) {
     if (ctx->ev_align_start[k]) (void)hipEventDestroy(ctx->ev_align_start[k]);
     if (ctx->ev_align_stop[k]) (void)hipEventDestroy(ctx->ev_align_stop[k]);
@@ -963,6 +965,44 @@ try {
   // which waits for the device by itself.
   ctx->frames.erase(it);
   ++ctx->handle_generation;
+  return SVOH_OK;
+} SVOH_ABI_CATCH(ctx)
+
+
+int svoh_mask_upload(svoh_ctx* ctx, int width, int height, int pitch, const uint8_t* data, svoh_mask_t* out_mask)
+try {
+  if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  SVOH_REQUIRE(ctx, data && out_mask, "NULL argument");
+  *out_mask = 0;
+  SVOH_REQUIRE(ctx, width >= 1 && height >= 1 && width < (1 << 14) && height < (1 << 14) && pitch >= width, "bad mask size or pitch");
+  SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  svoh::Mask m;
+  m.w = width; m.h = height;
+  SVOH_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&m.ptr), (size_t)width * height));
+  // pageable host memory: the copy has read `data` when the call returns
+  hipError_t e = hipMemcpy2DAsync(m.ptr, (size_t)width, data, (size_t)pitch, (size_t)width, (size_t)height, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) {
+    (void)hipFree(m.ptr);
+    return set_error(ctx, SVOH_ERR_HIP, "mask upload failed: %s", hipGetErrorString(e));
+  }
+  const uint64_t id = ctx->next_mask_id++;
+  ctx->masks.emplace(id, m);
+  *out_mask = id;
+  return SVOH_OK;
+} SVOH_ABI_CATCH(ctx)
+
+int svoh_mask_release(svoh_ctx* ctx, svoh_mask_t mask)
+try {
+  if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  auto it = ctx->masks.find(mask);
+  if (it == ctx->masks.end())
+    return set_error(ctx, SVOH_ERR_BAD_HANDLE, "unknown mask handle %llu", (unsigned long long)mask);
+  SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // a detector batch queued and not yet collected may still read the mask: the context's stream drains first
+  SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  (void)hipFree(it->second.ptr);
+  ctx->masks.erase(it);
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
 

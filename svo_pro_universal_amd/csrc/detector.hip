@@ -203,6 +203,28 @@ __global__ __launch_bounds__(256) void edge_select_batch_kernel(const float* __r
   edge_select_body(E + (size_t)blockIdx.z * map_stride_floats, w, h, border, threshold, init_score, g, corner_keys + (size_t)blockIdx.z * cell_stride);
 }
 
+// ---- camera masks between the phases (svoh_detect_cells_batch_masked) ----
+// fd_utils::fillFeatures (feature_detection_utils.cpp:97-115) drops a cell's winner when mask(y, x) == 0 at its level-0 pixel and
+// marks the grid cell only for the winners it keeps: the key of such a cell goes back to 0 ("no corner": free for the edgelet
+// phase; "no edgelet": nothing for the angle kernel to do).  One lane per (frame blockIdx.y, cell); the level-0 pixel is the one
+// decode_cells makes of the key on the host.  masks[frame] == NULL: the frame has no mask.
+__global__ __launch_bounds__(64) void mask_cells_batch_kernel(const uint8_t* const* __restrict__ masks, int w, int h, unsigned long long* __restrict__ keys,
+                                                              int n_cells, size_t cell_stride, int edges)
+{
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= n_cells) return;
+  const uint8_t* __restrict__ m = masks[blockIdx.y];
+  if (!m) return;
+  unsigned long long* p = keys + (size_t)blockIdx.y * cell_stride + k;
+  const unsigned long long key = *p;
+  if (key == 0ull) return;
+  const unsigned order = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
+  const int lv = edges ? 1 : (int)(order >> 28);   // an edgelet's key has no level bits: level 1, x * 2
+  const int x = (int)(order & 0x3FFFu) << lv, y = (int)((order >> 14) & 0x3FFFu) << lv;
+  // (a winner of a level of a w x h frame decodes to a pixel inside the mask; one that did not would have no mask pixel to pass: cleared)
+  if (x >= w || y >= h || m[(size_t)y * w + x] == 0) *p = 0ull;
+}
+
 // getAngleAtPixelUsingHistogram(img_pyr[1], (x, y), 4) for the winner of every cell (:831-839, 947-1009)
 template <bool BATCH>
 __device__ __forceinline__ void edge_angle_body(const DevImage& im, const unsigned long long* __restrict__ keys, int n_cells,
@@ -470,7 +492,9 @@ try {
 } SVOH_ABI_CATCH(nullptr)
 
 // the device half queued, nothing waited for: what comes back stands in ctx->h_detect behind ctx->ev_detect
-static int enqueue_detect_cells(svoh_ctx* ctx, int n_frames, const svoh_frame_t* frames, const svoh_detector_options* options, const uint8_t* occupancy)
+// masks: n_frames handles (0 = none) or NULL; without any mask nothing but the unmasked batch's work is queued
+static int enqueue_detect_cells(svoh_ctx* ctx, int n_frames, const svoh_frame_t* frames, const svoh_detector_options* options, const uint8_t* occupancy,
+                                const svoh_mask_t* masks)
 {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, n_frames >= 1 && n_frames <= 4096 && frames && options, "bad arguments");
@@ -492,6 +516,17 @@ static int enqueue_detect_cells(svoh_ctx* ctx, int n_frames, const svoh_frame_t*
     if (!fr[(size_t)i]) return set_error(ctx, SVOH_ERR_BAD_HANDLE, "unknown frame handle %llu", (unsigned long long)frames[i]);
     SVOH_REQUIRE(ctx, fr[(size_t)i]->lv[0].w == w && fr[(size_t)i]->lv[0].h == h && fr[(size_t)i]->n_levels == f0->n_levels, "the frames of a batch must be of one size");
   }
+  std::vector<const uint8_t*> mask_ptr;
+  if (masks)
+    for (int i = 0; i < n_frames; ++i) {
+      if (!masks[i]) continue;
+      auto it = ctx->masks.find(masks[i]);
+      if (it == ctx->masks.end()) return set_error(ctx, SVOH_ERR_BAD_HANDLE, "unknown mask handle %llu", (unsigned long long)masks[i]);
+      SVOH_REQUIRE(ctx, it->second.w == w && it->second.h == h, "a mask must have the size of its frame's level 0");
+      if (mask_ptr.empty()) mask_ptr.assign((size_t)n_frames, nullptr);
+      mask_ptr[(size_t)i] = it->second.ptr;
+    }
+  const bool masked = !mask_ptr.empty();
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int n_cols = (int)std::ceil((double)w / opt.cell_size), n_rows = (int)std::ceil((double)h / opt.cell_size);
   const int n_cells = n_cols * n_rows;
@@ -505,7 +540,9 @@ static int enqueue_detect_cells(svoh_ctx* ctx, int n_frames, const svoh_frame_t*
   const int n_lv = opt.max_level + 1 > 2 ? opt.max_level + 1 : 2;
   // device: [image table n_lv x n_frames | occupancy | corner keys | edge keys | angles | maps]; the first two travel up, keys and angles come back
   const size_t o_occ = (sizeof(DevImage) * (size_t)n_lv * nf + 255) & ~(size_t)255;
-  const size_t o_ck = (o_occ + cell_stride * nf + 255) & ~(size_t)255;
+  // (a masked batch: the table of the frames' mask pointers travels up behind the occupancy bytes)
+  const size_t o_mask = (o_occ + cell_stride * nf + 255) & ~(size_t)255;
+  const size_t o_ck = masked ? (o_mask + sizeof(const uint8_t*) * nf + 255) & ~(size_t)255 : o_mask;
   const size_t o_ek = o_ck + 8 * cell_stride * nf;
   const size_t o_ang = o_ek + 8 * cell_stride * nf;
   const size_t o_map = (o_ang + 4 * cell_stride * nf + 255) & ~(size_t)255;
@@ -522,6 +559,9 @@ static int enqueue_detect_cells(svoh_ctx* ctx, int n_frames, const svoh_frame_t*
     if (occupancy) for (int k = 0; k < n_cells; ++k) o[k] = occupancy[(size_t)i * n_cells + k] ? 1 : 0;
     else memset(o, 0, (size_t)n_cells);
   }
+  if (masked) memcpy(hs + o_mask, mask_ptr.data(), sizeof(const uint8_t*) * nf);
+  const uint8_t* const* d_masks = masked ? reinterpret_cast<const uint8_t* const*>(d + o_mask) : nullptr;   // (only a masked batch has the table)
+  const dim3 cell_grid((unsigned)((n_cells + 63) / 64), (unsigned)n_frames);
   SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d, hs, o_ck));
   SVOH_HIP_TRY(ctx, hipMemsetAsync(d + o_ck, 0, o_ang - o_ck, ctx->stream));
   const DevImage* d_tab = reinterpret_cast<const DevImage*>(d);
@@ -539,6 +579,7 @@ static int enqueue_detect_cells(svoh_ctx* ctx, int n_frames, const svoh_frame_t*
     hipLaunchKernelGGL(fast_select_batch_kernel, grid3d(im.w, im.h), dim3(256), 0, ctx->stream, static_cast<const uint8_t*>(S), map_bytes, im.w, im.h, l, opt.border,
                        (float)opt.threshold_primary, g, cell_stride);
   }
+  if (masked) hipLaunchKernelGGL(mask_cells_batch_kernel, cell_grid, dim3(64), 0, ctx->stream, d_masks, w, h, g.keys, n_cells, cell_stride, 0);
   SVOH_HIP_TRY(ctx, hipGetLastError());
   if (opt.detect_edgelets) {
     const DevImage& im = f0->lv[1];
@@ -548,7 +589,8 @@ static int enqueue_detect_cells(svoh_ctx* ctx, int n_frames, const svoh_frame_t*
     hipLaunchKernelGGL(edge_score_batch_kernel, grid3d(im.w, im.h), dim3(256), 0, ctx->stream, d_tab + nf, opt.border, (int)opt.threshold_secondary, E, map_bytes / sizeof(float));
     hipLaunchKernelGGL(edge_select_batch_kernel, grid3d(im.w, im.h), dim3(256), 0, ctx->stream, static_cast<const float*>(E), map_bytes / sizeof(float), im.w, im.h, opt.border,
                        (int)opt.threshold_secondary, (float)opt.threshold_secondary, ge, static_cast<const unsigned long long*>(g.keys), cell_stride);
-    hipLaunchKernelGGL(edge_angle_batch_kernel, dim3((unsigned)((n_cells + 63) / 64), (unsigned)n_frames), dim3(64), 0, ctx->stream, d_tab + nf,
+    if (masked) hipLaunchKernelGGL(mask_cells_batch_kernel, cell_grid, dim3(64), 0, ctx->stream, d_masks, w, h, ge.keys, n_cells, cell_stride, 1);
+    hipLaunchKernelGGL(edge_angle_batch_kernel, cell_grid, dim3(64), 0, ctx->stream, d_tab + nf,
                        static_cast<const unsigned long long*>(ge.keys), n_cells, reinterpret_cast<float*>(d + o_ang), cell_stride);
     SVOH_HIP_TRY(ctx, hipGetLastError());
   }
@@ -587,7 +629,13 @@ static int collect_detect_cells(svoh_ctx* ctx, uint64_t* corner_keys, uint64_t* 
 
 extern "C" int svoh_detect_cells_batch_enqueue(svoh_ctx* ctx, int n_frames, const svoh_frame_t* frames, const svoh_detector_options* options, const uint8_t* occupancy)
 try {
-  return enqueue_detect_cells(ctx, n_frames, frames, options, occupancy);
+  return enqueue_detect_cells(ctx, n_frames, frames, options, occupancy, nullptr);
+} SVOH_ABI_CATCH(ctx)
+
+extern "C" int svoh_detect_cells_batch_masked_enqueue(svoh_ctx* ctx, int n_frames, const svoh_frame_t* frames, const svoh_detector_options* options,
+                                                      const uint8_t* occupancy, const svoh_mask_t* masks)
+try {
+  return enqueue_detect_cells(ctx, n_frames, frames, options, occupancy, masks);
 } SVOH_ABI_CATCH(ctx)
 
 extern "C" int svoh_detect_cells_batch_collect(svoh_ctx* ctx, uint64_t* corner_keys, uint64_t* edge_keys, float* edge_angles)
@@ -600,7 +648,18 @@ extern "C" int svoh_detect_cells_batch(svoh_ctx* ctx, int n_frames, const svoh_f
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, corner_keys && options && (!options->detect_edgelets || (edge_keys && edge_angles)), "NULL output array (edgelets asked for: all three)");
-  const int rc = enqueue_detect_cells(ctx, n_frames, frames, options, occupancy);
+  const int rc = enqueue_detect_cells(ctx, n_frames, frames, options, occupancy, nullptr);
+  if (rc != SVOH_OK) return rc;
+  return collect_detect_cells(ctx, corner_keys, edge_keys, edge_angles);
+} SVOH_ABI_CATCH(ctx)
+
+extern "C" int svoh_detect_cells_batch_masked(svoh_ctx* ctx, int n_frames, const svoh_frame_t* frames, const svoh_detector_options* options,
+                                              const uint8_t* occupancy, const svoh_mask_t* masks, uint64_t* corner_keys, uint64_t* edge_keys,
+                                              float* edge_angles)
+try {
+  if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  SVOH_REQUIRE(ctx, corner_keys && options && (!options->detect_edgelets || (edge_keys && edge_angles)), "NULL output array (edgelets asked for: all three)");
+  const int rc = enqueue_detect_cells(ctx, n_frames, frames, options, occupancy, masks);
   if (rc != SVOH_OK) return rc;
   return collect_detect_cells(ctx, corner_keys, edge_keys, edge_angles);
 } SVOH_ABI_CATCH(ctx)

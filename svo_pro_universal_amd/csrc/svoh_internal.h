@@ -139,6 +139,12 @@ struct Frame {
   DevImage lv[SVOH_MAX_LEVELS];
 };
 
+// a camera's mask on the device (svoh_mask_upload): w x h bytes, rows w bytes apart
+struct Mask {
+  uint8_t* ptr = nullptr;
+  int w = 0, h = 0;
+};
+
 // grow-only device / pinned-host scratch buffers (never reallocated inside a
 // timed loop once warmed up).  A regrowth frees and allocates (0.3 - 1 ms, and hipFree waits for the device): a buffer
 // starts at 1 MB -- nothing next to 288 GB, and what a per-frame call of an EuRoC-sized front end never outgrows --
@@ -211,6 +217,8 @@ struct svoh_ctx {
   std::shared_ptr<svoh::SlabPool> slab_pool = std::make_shared<svoh::SlabPool>();   // declared before `frames`: outlives them
   std::unordered_map<uint64_t, svoh::Frame> frames;
   uint64_t next_frame_id = 1;
+  std::unordered_map<uint64_t, svoh::Mask> masks;   // svoh_mask_upload / _release
+  uint64_t next_mask_id = 1;
   // bumped whenever a frame or a feature set is released: what was derived from handles before (the staged batches' view
   // tables, matcher.hip) must be looked up again
   uint64_t handle_generation = 0;

@@ -162,6 +162,20 @@ class Context(object):
     def release_frame(self, frame):
         self._check(self.lib.svoh_release_frame(self.h, frame))
 
+    def upload_mask(self, mask):
+        """svoh_mask_upload: a camera's mask (HxW uint8 of the camera's size, 0 = never a feature here) onto the device,
+        once per camera.  Returns its handle (never 0: 0 stands for "no mask")."""
+        mask = np.asarray(mask)
+        if mask.ndim != 2 or mask.dtype != np.uint8:
+            raise ValueError("a mask is an HxW uint8 image")
+        mask = np.ascontiguousarray(mask)
+        out = capi.svoh_mask_t()
+        self._check(self.lib.svoh_mask_upload(self.h, mask.shape[1], mask.shape[0], mask.strides[0], mask.ctypes.data, C.byref(out)))
+        return out.value
+
+    def release_mask(self, mask):
+        self._check(self.lib.svoh_mask_release(self.h, mask))
+
     # ---- sparse image alignment --------------------------------------------
     def sparse_align(self, opt, problems):
         """problems: ctypes array of svoh_align_problem (see make_align_problems)."""
@@ -486,7 +500,77 @@ def _detect_features(self, opt, frame, width, height, occupancy=None, mask=None,
                 grad=grad[:2 * n].reshape(-1, 2).copy(), type=typ[:n].copy())
 
 
+def _cell_arrays(opt, n, width, height):
+    n_cells = int(np.ceil(width / opt.cell_size)) * int(np.ceil(height / opt.cell_size))
+    return np.zeros((n, n_cells), np.uint64), np.zeros((n, n_cells), np.uint64), np.zeros((n, n_cells), np.float32)
+
+
+def _batch_inputs(frames, occupancy, masks):
+    """(n, frame handles, occupancy array or None, mask handles or None) as the batched detector's entries take them."""
+    n = len(frames)
+    fr = (capi.svoh_frame_t * n)(*frames)
+    occ = None if occupancy is None else np.ascontiguousarray(occupancy, np.uint8)
+    if masks is not None and len(masks) != n:
+        raise ValueError("masks: one handle per frame (0 = none)")
+    mk = None if masks is None else (capi.svoh_mask_t * n)(*[int(m) for m in masks])
+    return n, fr, occ, mk
+
+
+def _detect_cells_batch_enqueue(self, opt, frames, occupancy=None, masks=None):
+    """svoh_detect_cells_batch_enqueue, or svoh_detect_cells_batch_masked_enqueue when masks (one handle of upload_mask per
+    frame, 0 = none) is given: the device half of the detector for many frames of one size, queued."""
+    n, fr, occ, mk = _batch_inputs(frames, occupancy, masks)
+    o = None if occ is None else occ.ctypes.data
+    if mk is None:
+        self._check(self.lib.svoh_detect_cells_batch_enqueue(self.h, n, fr, C.byref(opt), o))
+    else:
+        self._check(self.lib.svoh_detect_cells_batch_masked_enqueue(self.h, n, fr, C.byref(opt), o, mk))
+
+
+def _detect_cells_batch_collect(self, opt, n_frames, width, height):
+    """svoh_detect_cells_batch_collect: (corner_keys, edge_keys, edge_angles), n_frames x n_cells each."""
+    ck, ek, ang = _cell_arrays(opt, n_frames, width, height)
+    self._check(self.lib.svoh_detect_cells_batch_collect(self.h, ck.ctypes.data, ek.ctypes.data, ang.ctypes.data))
+    return ck, ek, ang
+
+
+def _detect_cells_batch(self, opt, frames, width, height, occupancy=None, masks=None):
+    """svoh_detect_cells_batch / svoh_detect_cells_batch_masked (masks: one handle per frame, 0 = none): blocking."""
+    n, fr, occ, mk = _batch_inputs(frames, occupancy, masks)
+    o = None if occ is None else occ.ctypes.data
+    ck, ek, ang = _cell_arrays(opt, n, width, height)
+    if mk is None:
+        self._check(self.lib.svoh_detect_cells_batch(self.h, n, fr, C.byref(opt), o, ck.ctypes.data, ek.ctypes.data, ang.ctypes.data))
+    else:
+        self._check(self.lib.svoh_detect_cells_batch_masked(self.h, n, fr, C.byref(opt), o, mk, ck.ctypes.data, ek.ctypes.data, ang.ctypes.data))
+    return ck, ek, ang
+
+
+def detect_fill_features(opt, width, height, corner_keys, edge_keys, edge_angles, max_n_features=None, lib=None):
+    """svoh_detect_fill_features: the host half for ONE frame's cell arrays; the dict detect_features gives."""
+    lib = lib or capi.load()
+    n_cells = int(np.ceil(width / opt.cell_size)) * int(np.ceil(height / opt.cell_size))
+    if max_n_features is None:
+        max_n_features = n_cells
+    ck = np.ascontiguousarray(corner_keys, np.uint64); ek = np.ascontiguousarray(edge_keys, np.uint64)
+    ang = np.ascontiguousarray(edge_angles, np.float32)
+    px = np.zeros(2 * n_cells); score = np.zeros(n_cells); level = np.zeros(n_cells, np.int32)
+    grad = np.zeros(2 * n_cells); typ = np.zeros(n_cells, np.uint8)
+    n = C.c_int32()
+    rc = lib.svoh_detect_fill_features(C.byref(opt), int(width), int(height), ck.ctypes.data, ek.ctypes.data, ang.ctypes.data,
+                                       int(min(max_n_features, n_cells)), px.ctypes.data, score.ctypes.data, level.ctypes.data,
+                                       grad.ctypes.data, typ.ctypes.data, C.byref(n))
+    if rc != 0:
+        raise SvohError(rc, lib.svoh_last_error_string(None).decode())
+    n = n.value
+    return dict(px=px[:2 * n].reshape(-1, 2).copy(), score=score[:n].copy(), level=level[:n].copy(),
+                grad=grad[:2 * n].reshape(-1, 2).copy(), type=typ[:n].copy())
+
+
 Context.epipolar_match_batch = _epipolar_match_batch
+Context.detect_cells_batch = _detect_cells_batch
+Context.detect_cells_batch_enqueue = _detect_cells_batch_enqueue
+Context.detect_cells_batch_collect = _detect_cells_batch_collect
 Context.detect_features = _detect_features
 Context.optimize_pose = _optimize_pose
 Context.optimize_points = _optimize_points

@@ -672,7 +672,7 @@ void DetectorHip::detect(const FramePtr& frame)
   std::vector<uint8_t> type = std::move(frame->type_vec_);
   px.resize(2 * frame->num_features_); score.resize(frame->num_features_); grad.resize(2 * frame->num_features_);
   level.resize(frame->num_features_); type.resize(frame->num_features_);
-  detect(frame->pyramid, nullptr, 0, grid_.size(), px, score, level, grad, type);
+  detect(frame->pyramid, frame->maskData(), frame->maskPitch(), grid_.size(), px, score, level, grad, type);
   frame->px_vec_ = px; frame->score_vec_ = score; frame->grad_vec_ = grad; frame->level_vec_ = level; frame->type_vec_ = type;
   frame->num_features_ = level.size();
   frame->landmark_vec_.assign(frame->num_features_, nullptr);
@@ -837,7 +837,7 @@ void StereoTriangulationHip::compute(const FramePtr& frame0, const FramePtr& fra
   std::vector<int32_t> new_levels;
   std::vector<uint8_t> new_types;
   const size_t max_n_features = feature_detector_->grid_.size();
-  feature_detector_->detect(frame0->pyramid, nullptr, 0, max_n_features, new_px, new_scores, new_levels, new_grads, new_types);
+  feature_detector_->detect(frame0->pyramid, frame0->maskData(), frame0->maskPitch(), max_n_features, new_px, new_scores, new_levels, new_grads, new_types);
   Job job;
   if (!prepare(frame0, frame1, new_px, new_scores, new_levels, new_grads, new_types, &job)) return;
 
@@ -1038,7 +1038,7 @@ void initializeSeeds(const FramePtr& frame, DetectorHip& feature_detector, size_
   std::vector<double> px, score, grad;
   std::vector<int32_t> level;
   std::vector<uint8_t> type;
-  feature_detector.detect(frame->pyramid, nullptr, 0, static_cast<size_t>(max_n_features), px, score, level, grad, type);
+  feature_detector.detect(frame->pyramid, frame->maskData(), frame->maskPitch(), static_cast<size_t>(max_n_features), px, score, level, grad, type);
   appendSeeds(frame, px, score, level, grad, type, depth_min, depth_mean);
 }
 

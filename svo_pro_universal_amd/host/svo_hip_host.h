@@ -34,11 +34,18 @@ namespace detail { struct SpeculativeMatches; struct Resolved; }   // svo_hip_ho
 
 using Transformation = svoh::Rigid;  // minkindr QuatTransformation semantics (svoh_math.h)
 
+// an 8-bit grey image on the host: what the image readers of svo_hip_io.h hand out, and a camera's mask
+struct GrayImage { int width = 0, height = 0; std::vector<uint8_t> data; };
+using CameraMaskPtr = std::shared_ptr<const GrayImage>;
+
 // The members of svo::Frame that SparseImgAlign::run reads (frame.h:46-73, 252-306).
 struct Frame {
   svoh_frame_t pyramid = 0;      // device copy of img_pyr_
   svoh_features_t features = 0;  // device copy of px_vec_ / f_vec_ / grad_vec_ / level_vec_ of a keyframe whose features are final (svoh_features_upload), or 0
   svoh_camera cam{};             // cam()
+  CameraMaskPtr mask;            // getMask(): the camera's mask (its size; 0 = never a feature here), or null: every detector run on this frame takes it
+  const uint8_t* maskData() const { return mask && !mask->data.empty() ? mask->data.data() : nullptr; }
+  int maskPitch() const { return mask ? mask->width : 0; }
   Transformation T_f_w_{ {1, 0, 0, 0}, {0, 0, 0} };
   Transformation T_cam_imu_{ {1, 0, 0, 0}, {0, 0, 0} };
   Transformation T_imu_cam_{ {1, 0, 0, 0}, {0, 0, 0} };

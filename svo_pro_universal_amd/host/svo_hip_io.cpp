@@ -266,9 +266,12 @@ std::vector<RigCamera> cameraRigFromYaml(const YamlNode& root)
 {
   std::vector<RigCamera> rig;
   const YamlNode& cams = root["cameras"];
-  if (cams.kind != YamlNode::kSeq || cams.seq.empty()) throw std::runtime_error("calibration: no 'cameras' sequence");
-  for (const YamlNode& entry : cams.seq) {
-    const YamlNode& c = entry["camera"];
+  // a single-camera document (CameraGeometryBase::loadFromYaml): the camera's own keys at the top level
+  const bool single = cams.isNull() && root.has("intrinsics");
+  if (!single && (cams.kind != YamlNode::kSeq || cams.seq.empty())) throw std::runtime_error("calibration: no 'cameras' sequence");
+  const std::vector<YamlNode> one(1);
+  for (const YamlNode& entry : single ? one : cams.seq) {
+    const YamlNode& c = single ? root : entry["camera"];
     if (c.isNull()) throw std::runtime_error("calibration: entry without 'camera'");
     RigCamera rc;
     rc.label = c["label"].asString("cam");
@@ -309,11 +312,34 @@ std::vector<RigCamera> cameraRigFromYaml(const YamlNode& root)
     } else if (!entry["T_B_C"].isNull()) {
       throw std::runtime_error("calibration: T_B_C needs 16 numbers");
     }
+    if (c.has("mask")) {
+      rc.mask_file = c["mask"].asString("");
+      if (rc.mask_file.empty()) throw std::runtime_error("calibration: empty 'mask' key");
+    }
     rig.push_back(rc);
   }
   return rig;
 }
-std::vector<RigCamera> loadCameraRig(const std::string& path) { return cameraRigFromYaml(loadYamlFile(path)); }
+
+std::vector<RigCamera> loadCameraRig(const std::string& path)
+{
+  std::vector<RigCamera> rig = cameraRigFromYaml(loadYamlFile(path));
+  const size_t slash = path.find_last_of('/');
+  const std::string dir = slash == std::string::npos ? std::string(".") : path.substr(0, slash);
+  for (RigCamera& rc : rig) {
+    if (rc.mask_file.empty()) continue;
+    const std::string file = rc.mask_file[0] == '/' ? rc.mask_file : dir + "/" + rc.mask_file;
+    try {
+      rc.mask = readPngGray(file);
+    } catch (const std::exception& e) {
+      throw std::runtime_error("calibration: unable to load mask file '" + file + "' of camera '" + rc.label + "': " + e.what());
+    }
+    if (rc.mask.width != rc.cam.width || rc.mask.height != rc.cam.height || rc.mask.data.size() != (size_t)rc.cam.width * (size_t)rc.cam.height)
+      throw std::runtime_error("calibration: mask '" + file + "' is " + std::to_string(rc.mask.width) + " x " + std::to_string(rc.mask.height) + ", camera '" +
+                               rc.label + "' is " + std::to_string(rc.cam.width) + " x " + std::to_string(rc.cam.height));
+  }
+  return rig;
+}
 
 // ---------------------------------------------------------------------------
 // svo_factory.cpp:107-310, the keys this library consumes

@@ -41,13 +41,28 @@ struct YamlNode {
 YamlNode parseYaml(const std::string& text);
 YamlNode loadYamlFile(const std::string& path);
 
+// ---- images ----
+using GrayImage = svo_hip::GrayImage;   // (svo_hip_host.h)
+GrayImage readPngGray(const std::string& path);                     // throws std::runtime_error
+GrayImage decodePngGray(const uint8_t* bytes, size_t n_bytes);
+
 // ---- camera rig ----
 struct RigCamera {
   std::string label;
   svoh_camera cam{};
   Transformation T_B_C{ { 1, 0, 0, 0 }, { 0, 0, 0 } };   // body <- camera (T_imu_cam)
+  // the camera's mask (camera_geometry_base.cpp:62-76): an 8-bit image of the camera's size, 0 = never a feature here; empty = none.
+  // mask_file is the `mask:` key as the file has it; loadCameraRig reads the image, relative to the calibration file's directory.
+  std::string mask_file;
+  GrayImage mask;
+  // the mask as a Frame carries it (Frame::mask), or null without one
+  CameraMaskPtr maskPtr() const { return mask.data.empty() ? CameraMaskPtr() : std::make_shared<const GrayImage>(mask); }
 };
+// Both documents the reference loads: an NCamera (`cameras:` sequence, a `mask:` key inside a `camera:` node, ncamera.cpp:44-48)
+// and a single camera (the camera's keys and `mask:` at the top level, camera_geometry_base.cpp:33-37; T_B_C = identity).
+// A mask that cannot be read, or whose size is not the camera's, is an error ("Unable to load mask file", CHECK_EQ rows / cols).
 std::vector<RigCamera> loadCameraRig(const std::string& calib_yaml_path);
+// the same from a parsed document: without a directory to resolve `mask:` against, it records mask_file and leaves mask empty
 std::vector<RigCamera> cameraRigFromYaml(const YamlNode& root);
 
 // ---- the front-end options of svo_factory.cpp, for the parts this library implements ----
@@ -68,11 +83,6 @@ struct FrontendParams {
 };
 FrontendParams frontendParamsFromYaml(const YamlNode& node);
 FrontendParams loadFrontendParams(const std::string& param_yaml_path);
-
-// ---- images ----
-struct GrayImage { int width = 0, height = 0; std::vector<uint8_t> data; };
-GrayImage readPngGray(const std::string& path);                     // throws std::runtime_error
-GrayImage decodePngGray(const uint8_t* bytes, size_t n_bytes);
 
 // ---- EuRoC ASL folder (<root>/mav0/cam0/data.csv, <root>/mav0/cam0/data/<timestamp>.png) ----
 struct EurocSequence {

@@ -75,6 +75,9 @@ struct FrontendLockstep::Stream {
   int pose_slot = -1;
   bool want_kf = false;
   int detect_slot = -1;
+  CameraMaskPtr mask;            // the stream's camera mask, or null ...
+  svoh_mask_t mask_handle = 0;   // ... and its copy on the device (shared by the streams with the same image)
+  std::vector<FrontendLockstep::NewFeature> new_features;
   int detect_max_n = 0;
   // the depth-filter update in flight
   std::vector<FramePtr> seed_frames;
@@ -152,7 +155,44 @@ FrontendLockstep::FrontendLockstep(svoh_ctx* ctx, int n_streams, const LockstepO
     ropt.affine_est_gain = so.params.reprojector_affine_est_gain;
     streams_.emplace_back(new Stream(ctx_, opt_, so, ropt));
     streams_.back()->reprojector.sortPlannedListsOnly(true);
+    streams_.back()->mask = so.own_camera ? so.mask : opt_.mask;
+    streams_.back()->mask_handle = maskHandleFor(streams_.back()->mask);
   }
+}
+
+// the device copy of a mask image: streams whose masks are the same image (the same object or equal bytes) share one upload
+svoh_mask_t FrontendLockstep::maskHandleFor(const CameraMaskPtr& m)
+{
+  if (!m || m->data.empty()) return 0;
+  if (m->width != opt_.cam.width || m->height != opt_.cam.height || m->data.size() != static_cast<size_t>(m->width) * static_cast<size_t>(m->height))
+    throw std::runtime_error("FrontendLockstep: a camera mask must have the camera's image size");
+  for (const auto& e : masks_)
+    if (e.first == m || (e.first->width == m->width && e.first->height == m->height && e.first->data == m->data)) return e.second;
+  svoh_mask_t h = 0;
+  check(svoh_mask_upload(ctx_, m->width, m->height, m->width, m->data.data(), &h), "svoh_mask_upload");
+  masks_.emplace_back(m, h);
+  return h;
+}
+
+void FrontendLockstep::setStreamMask(int s, int width, int height, int pitch, const uint8_t* data)
+{
+  if (s < 0 || s >= numStreams()) throw std::runtime_error("FrontendLockstep::setStreamMask: no such stream");
+  Stream& st = *streams_[static_cast<size_t>(s)];
+  if (st.k != 0 || st.frame) throw std::runtime_error("FrontendLockstep::setStreamMask: the stream has taken frames already");
+  if (!data) { st.mask.reset(); st.mask_handle = 0; return; }
+  if (width < 1 || height < 1 || pitch < width) throw std::runtime_error("FrontendLockstep::setStreamMask: bad mask size or pitch");
+  auto img = std::make_shared<GrayImage>();
+  img->width = width; img->height = height; img->data.resize(static_cast<size_t>(width) * static_cast<size_t>(height));
+  for (int y = 0; y < height; ++y) memcpy(img->data.data() + static_cast<size_t>(y) * width, data + static_cast<size_t>(y) * pitch, static_cast<size_t>(width));
+  st.mask_handle = maskHandleFor(img);
+  st.mask = img;
+}
+
+std::vector<FrontendLockstep::NewFeature> FrontendLockstep::newKeyframeFeatures(int s)
+{
+  std::vector<NewFeature> out;
+  out.swap(streams_.at(static_cast<size_t>(s))->new_features);
+  return out;
 }
 
 FrontendLockstep::~FrontendLockstep()
@@ -169,6 +209,7 @@ FrontendLockstep::~FrontendLockstep()
   // stream waits for it (on the device) before the slab goes back to the pool, where the next build would reuse it unordered
   (void)svoh_prefetch_fence(ctx_);
   for (svoh_frame_t h : prefetched_) if (h) (void)svoh_release_frame(ctx_, h);
+  for (const auto& e : masks_) (void)svoh_mask_release(ctx_, e.second);
 }
 
 void FrontendLockstep::drainReleases()
@@ -294,7 +335,12 @@ void FrontendLockstep::startDetection(const std::vector<int>& which)
   std::vector<svoh_frame_t> frames(n);
   for (size_t i = 0; i < n; ++i) frames[i] = streams_[static_cast<size_t>(detect_.streams[i])]->frame->pyramid;
   const svoh_detector_options dopt = streams_[0]->detector.abiOptions();
-  check(svoh_detect_cells_batch_enqueue(ctx_, static_cast<int>(n), frames.data(), &dopt, detect_.occ.data()), "svoh_detect_cells_batch_enqueue");
+  // a round without a masked stream queues the unmasked batch, as before there were masks
+  std::vector<svoh_mask_t> masks(n);
+  bool any_mask = false;
+  for (size_t i = 0; i < n; ++i) { masks[i] = streams_[static_cast<size_t>(detect_.streams[i])]->mask_handle; any_mask = any_mask || masks[i] != 0; }
+  if (any_mask) check(svoh_detect_cells_batch_masked_enqueue(ctx_, static_cast<int>(n), frames.data(), &dopt, detect_.occ.data(), masks.data()), "svoh_detect_cells_batch_masked_enqueue");
+  else check(svoh_detect_cells_batch_enqueue(ctx_, static_cast<int>(n), frames.data(), &dopt, detect_.occ.data()), "svoh_detect_cells_batch_enqueue");
   ++device_calls_;
   detect_.in_flight = true;
 }
@@ -363,6 +409,11 @@ void FrontendLockstep::makeKeyframes(const std::vector<int>& which)
       st.detector.fillFromCells(ckeys.data() + i * n_cells, ekeys.data() + i * n_cells, angles.data() + i * n_cells, opt_.cam.width, opt_.cam.height,
                                 static_cast<size_t>(st.detect_max_n), px, score, level, grad, type);
       depth_filter_utils::appendSeeds(f, px, score, level, grad, type, st.so.depth_min, st.so.depth_mean);
+      if (opt_.log_new_features)
+        for (size_t q = n_old; q < f->num_features_; ++q) {   // as the frame holds them: the seeds appendSeeds made of the detector's features
+          NewFeature nf; nf.k = static_cast<size_t>(f->id_); nf.x = f->px_vec_[2 * q]; nf.y = f->px_vec_[2 * q + 1]; nf.type = f->type_vec_[q];
+          st.new_features.push_back(nf);
+        }
     } else {
       st.detector.resetGrid();
     }
@@ -485,6 +536,7 @@ void FrontendLockstep::addImages(const uint8_t* const* images, int pitch, const 
       });
       frame->pyramid = handles[static_cast<size_t>(s)];
       frame->cam = st.so.own_camera ? st.so.cam : opt_.cam;
+      frame->mask = st.mask;
       frame->set_T_cam_imu(svoh::inverse(st.so.own_camera ? st.so.T_B_C : opt_.T_B_C));
       frame->id_ = static_cast<int>(st.k);
       st.frame = frame;
@@ -1197,6 +1249,22 @@ int svohl_run_schedule(svohl_engine* e, const uint8_t* base, size_t image_bytes,
       }
     }
     if (frames_done) *frames_done = done;
+  });
+}
+
+int svohl_set_stream_mask(svohl_engine* e, int stream, int width, int height, int pitch, const uint8_t* data)
+{
+  return svohl_guard([&] {
+    if (!e) throw std::runtime_error("svohl_set_stream_mask: NULL engine");
+    e->fe->setStreamMask(stream, width, height, pitch, data);
+  });
+}
+
+int svohl_masks_on_device(svohl_engine* e, int* n_masks)
+{
+  return svohl_guard([&] {
+    if (!e || !n_masks) throw std::runtime_error("svohl_masks_on_device: NULL argument");
+    *n_masks = static_cast<int>(e->fe->masksOnDevice());
   });
 }
 

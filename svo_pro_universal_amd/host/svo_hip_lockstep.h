@@ -57,6 +57,7 @@ struct LockstepStreamOptions {
   bool own_camera = false;
   svoh_camera cam{};
   Transformation T_B_C{ { 1, 0, 0, 0 }, { 0, 0, 0 } };
+  CameraMaskPtr mask;   // the own camera's mask (io::RigCamera::maskPtr()), or null; read with own_camera, like cam and T_B_C
 };
 
 struct LockstepOptions {
@@ -64,6 +65,11 @@ struct LockstepOptions {
   io::FrontendParams params;
   svoh_camera cam{};
   Transformation T_B_C{ { 1, 0, 0, 0 }, { 0, 0, 0 } };
+  // the camera's mask (frame->getMask(): every detector run takes it), or null.  The engine uploads one mask per DISTINCT camera mask of its
+  // streams (svoh_mask_upload; streams that share an image share the upload) and releases them with itself; the round's keyframes are
+  // detected by svoh_detect_cells_batch_masked_enqueue with a handle per frame (0 for a stream without a mask)
+  CameraMaskPtr mask;
+  bool log_new_features = false;   // keep what every keyframe's detection added (newKeyframeFeatures), for harnesses that write it out
   float depth_min = 1.f, depth_mean = 2.f, depth_max = 4.f;   // the depth prior of a new keyframe's seeds
   size_t kf_every = 8, min_tracked = 60;                     // the harness' keyframe rule
   int n_workers = 1;                                          // host threads, the caller included (a pool of the engine's own)
@@ -117,6 +123,12 @@ class FrontendLockstep {
   // Rows are complete once the frame's depth-filter update has been finished, i.e. at the start of the next addImages (or
   // in finish()): completedRows(s) hands out, and forgets, the rows of stream s that became complete since the last call.
   std::vector<FrameRow> completedRows(int s);
+  // with LockstepOptions::log_new_features: the features the detector added at stream s' keyframes since the last call (level-0 pixels)
+  struct NewFeature { size_t k = 0; double x = 0, y = 0; int type = 0; };
+  std::vector<NewFeature> newKeyframeFeatures(int s);
+  // a stream's mask given after construction and before the stream's first frame (the C face: svohl_set_stream_mask); copies the image
+  void setStreamMask(int s, int width, int height, int pitch, const uint8_t* data);
+  size_t masksOnDevice() const { return masks_.size(); }
   const RoundTimes& lastRoundTimes() const { return times_; }
   size_t keyframesAlive(int s) const;
   // waits for the depth-filter update in flight and completes the last rows
@@ -135,6 +147,9 @@ class FrontendLockstep {
   void finishStructure();
   size_t structure_in_flight_ = 0;   // points of the batch in flight
   std::vector<int> structure_streams_;
+  // one device mask per distinct mask image of the streams
+  std::vector<std::pair<CameraMaskPtr, svoh_mask_t>> masks_;
+  svoh_mask_t maskHandleFor(const CameraMaskPtr& m);
   void startDetection(const std::vector<int>& which);
   void makeKeyframes(const std::vector<int>& which);
   // the detector batch of the round's new keyframes between its two halves

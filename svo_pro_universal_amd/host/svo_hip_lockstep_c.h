@@ -60,6 +60,11 @@ int svohl_run_sequence(svohl_engine* e, const uint8_t* base, size_t image_bytes,
  * read for a stream in the round of its first frame.  *frames_done (may be NULL): frames taken by all streams in these rounds. */
 int svohl_run_schedule(svohl_engine* e, const uint8_t* base, size_t image_bytes, size_t stream_stride, int n_frames, int pitch, long k_first, int n_rounds,
                        const int* start, const int* step, const int* every, const int* phase, const svoh_se3* T_f_w_first, double* round_ms, long* frames_done);
+/* The mask of stream s' camera (width x height bytes, `pitch` bytes per row, 0 = never a feature here; the camera's image size), given after the
+ * engine is made and before the stream's first frame; data == NULL takes it away.  The engine copies the image and keeps one upload per
+ * distinct mask on the device (streams given equal masks share it), released with the engine; the keyframes' detector takes it. */
+int svohl_set_stream_mask(svohl_engine* e, int stream, int width, int height, int pitch, const uint8_t* data);
+int svohl_masks_on_device(svohl_engine* e, int* n_masks);
 int svohl_pose(svohl_engine* e, int stream, svoh_se3* T_f_w);
 /* pyramid, align, reproject, pose, seeds, keyframe, total of the last round (ms) and its device calls */
 int svohl_last_round(svohl_engine* e, double times_ms[7], int* device_calls);
@@ -87,6 +92,8 @@ int svohs_create_rigs(svoh_ctx* ctx, int n_streams, const svoh_camera* cams, con
 void svohs_destroy(svohs_engine* e);
 int svohs_run_sequence(svohs_engine* e, const uint8_t* base, size_t image_bytes, size_t stream_stride, int n_pairs, int pitch, long k_first, int n_rounds,
                        const svoh_se3* T_imu_world_first, const double* prior_forward, double* round_ms);
+/* as svohl_set_stream_mask, for camera `cam` (0 left, 1 right) of stream s' rig */
+int svohs_set_stream_mask(svohs_engine* e, int stream, int cam, int width, int height, int pitch, const uint8_t* data);
 int svohs_pose(svohs_engine* e, int stream, svoh_se3* T_imu_world);
 int svohs_phase_times(svohs_engine* e, double* ms /* 8: pyramids, finish seeds, align, reproject, pose, structure, keyframes, seed updates */);
 int svohs_finish(svohs_engine* e);

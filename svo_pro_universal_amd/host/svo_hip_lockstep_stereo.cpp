@@ -118,6 +118,43 @@ FrontendLockstepStereo::FrontendLockstepStereo(svoh_ctx* ctx, int n_streams, con
   opt_.params.img_align.estimate_illumination_offset = true;
   pool_.reset(new WorkerPool(opt_.n_workers < 1 ? 1 : opt_.n_workers, false));
   for (int s = 0; s < n_streams; ++s) streams_.emplace_back(new Stream(ctx_, opt_));
+  mask_handles_.assign(static_cast<size_t>(n_streams), std::array<svoh_mask_t, 2>{ { 0, 0 } });
+  stream_masks_.resize(static_cast<size_t>(n_streams));
+  std::vector<std::array<CameraMaskPtr, 2>> of_rig(opt_.per_stream_rig.empty() ? 1 : opt_.per_stream_rig.size());   // one copy per rig, not per stream
+  for (size_t r = 0; r < of_rig.size(); ++r)
+    for (int c = 0; c < 2; ++c) of_rig[r][static_cast<size_t>(c)] = rigOf(static_cast<int>(r))[static_cast<size_t>(c)].maskPtr();
+  for (int s = 0; s < n_streams; ++s)
+    for (size_t c = 0; c < 2; ++c) {
+      stream_masks_[static_cast<size_t>(s)][c] = of_rig[opt_.per_stream_rig.empty() ? 0 : static_cast<size_t>(s)][c];
+      mask_handles_[static_cast<size_t>(s)][c] = maskHandleFor(stream_masks_[static_cast<size_t>(s)][c]);
+    }
+}
+
+svoh_mask_t FrontendLockstepStereo::maskHandleFor(const CameraMaskPtr& m)
+{
+  if (!m || m->data.empty()) return 0;
+  if (m->width != opt_.rig[0].cam.width || m->height != opt_.rig[0].cam.height || m->data.size() != static_cast<size_t>(m->width) * static_cast<size_t>(m->height))
+    throw std::runtime_error("FrontendLockstepStereo: a camera mask must have the cameras' image size");
+  for (const auto& e : masks_)
+    if (e.first == m || (e.first->width == m->width && e.first->height == m->height && e.first->data == m->data)) return e.second;
+  svoh_mask_t h = 0;
+  check(svoh_mask_upload(ctx_, m->width, m->height, m->width, m->data.data(), &h), "svoh_mask_upload");
+  masks_.emplace_back(m, h);
+  return h;
+}
+
+void FrontendLockstepStereo::setStreamMask(int s, int c, int width, int height, int pitch, const uint8_t* data)
+{
+  if (s < 0 || s >= numStreams() || c < 0 || c > 1) throw std::runtime_error("FrontendLockstepStereo::setStreamMask: no such stream / camera");
+  if (streams_[static_cast<size_t>(s)]->bundle || streams_[static_cast<size_t>(s)]->last) throw std::runtime_error("FrontendLockstepStereo::setStreamMask: the stream has taken pairs already");
+  CameraMaskPtr& slot = stream_masks_[static_cast<size_t>(s)][static_cast<size_t>(c)];
+  if (!data) { slot.reset(); mask_handles_[static_cast<size_t>(s)][static_cast<size_t>(c)] = 0; return; }
+  if (width < 1 || height < 1 || pitch < width) throw std::runtime_error("FrontendLockstepStereo::setStreamMask: bad mask size or pitch");
+  auto img = std::make_shared<GrayImage>();
+  img->width = width; img->height = height; img->data.resize(static_cast<size_t>(width) * static_cast<size_t>(height));
+  for (int y = 0; y < height; ++y) memcpy(img->data.data() + static_cast<size_t>(y) * width, data + static_cast<size_t>(y) * pitch, static_cast<size_t>(width));
+  mask_handles_[static_cast<size_t>(s)][static_cast<size_t>(c)] = maskHandleFor(img);
+  slot = img;
 }
 
 FrontendLockstepStereo::~FrontendLockstepStereo()
@@ -132,6 +169,7 @@ FrontendLockstepStereo::~FrontendLockstepStereo()
     if (st->last) for (const FramePtr& f : st->last->frames_) for (auto& sr : f->seed_ref_vec_) sr.keyframe.reset();
   }
   streams_.clear();
+  for (const auto& e : masks_) (void)svoh_mask_release(ctx_, e.second);
   drainReleases();
 }
 
@@ -212,21 +250,28 @@ void FrontendLockstepStereo::makeKeyframes(const std::vector<std::pair<int, size
   std::vector<uint8_t> occ;
   std::vector<uint64_t> ckeys, ekeys;
   std::vector<float> angles;
-  auto detect_cells = [&](const std::function<bool(size_t)>& wanted, const std::function<svoh_frame_t(size_t)>& pyramid_of, DetectorHip& options_of) {
+  // (cam_of(w): which camera of the stream's rig the frame is from -- its mask goes with it)
+  auto detect_cells = [&](const std::function<bool(size_t)>& wanted, const std::function<svoh_frame_t(size_t)>& pyramid_of, const std::function<size_t(size_t)>& cam_of,
+                          DetectorHip& options_of) {
     std::vector<svoh_frame_t> frames;
+    std::vector<svoh_mask_t> masks;
+    bool any_mask = false;
     std::vector<uint8_t> packed;
     for (size_t w = 0; w < K; ++w) {
       work[w].slot = -1;
       if (!wanted(w)) continue;
       work[w].slot = static_cast<int>(frames.size());
       frames.push_back(pyramid_of(w));
+      masks.push_back(mask_handles_[static_cast<size_t>(which[w].first)][cam_of(w)]);
+      any_mask = any_mask || masks.back() != 0;
       packed.insert(packed.end(), occ.begin() + static_cast<long>(w * n_cells), occ.begin() + static_cast<long>((w + 1) * n_cells));
     }
     const size_t n = frames.size();
     ckeys.assign(n * n_cells, 0); ekeys.assign(n * n_cells, 0); angles.assign(n * n_cells, 0.f);
     if (!n) return;
     const svoh_detector_options dopt = options_of.abiOptions();
-    check(svoh_detect_cells_batch_enqueue(ctx_, static_cast<int>(n), frames.data(), &dopt, packed.data()), "svoh_detect_cells_batch_enqueue");
+    if (any_mask) check(svoh_detect_cells_batch_masked_enqueue(ctx_, static_cast<int>(n), frames.data(), &dopt, packed.data(), masks.data()), "svoh_detect_cells_batch_masked_enqueue");
+    else check(svoh_detect_cells_batch_enqueue(ctx_, static_cast<int>(n), frames.data(), &dopt, packed.data()), "svoh_detect_cells_batch_enqueue");
     check(svoh_detect_cells_batch_collect(ctx_, ckeys.data(), ekeys.data(), angles.data()), "svoh_detect_cells_batch_collect");
     ++device_calls_;
   };
@@ -252,7 +297,7 @@ void FrontendLockstepStereo::makeKeyframes(const std::vector<std::pair<int, size
   });
   refresh([&](size_t w) { return stream_of(w).bundle->at(1 - which[w].second); });
   // ---- stereo triangulation (:146-155): new features where the left frame has none, all streams' epipolar searches in one launch
-  detect_cells([&](size_t w) { return work[w].tri; }, [&](size_t w) { return stream_of(w).bundle->at(0)->pyramid; }, *stream_of(0).tri_detector);
+  detect_cells([&](size_t w) { return work[w].tri; }, [&](size_t w) { return stream_of(w).bundle->at(0)->pyramid; }, [](size_t) { return static_cast<size_t>(0); }, *stream_of(0).tri_detector);
   pool_->run(static_cast<int>(K), [&](int wi) {
     const size_t w = static_cast<size_t>(wi);
     if (!work[w].tri) return;
@@ -327,7 +372,7 @@ void FrontendLockstepStereo::makeKeyframes(const std::vector<std::pair<int, size
     st.seed_detector.occupancyBytes(occ.data() + w * n_cells);
   });
   refresh([&](size_t w) { return stream_of(w).bundle->at(which[w].second); });
-  detect_cells([&](size_t w) { return work[w].seeds; }, [&](size_t w) { return stream_of(w).bundle->at(which[w].second)->pyramid; }, stream_of(0).seed_detector);
+  detect_cells([&](size_t w) { return work[w].seeds; }, [&](size_t w) { return stream_of(w).bundle->at(which[w].second)->pyramid; }, [&](size_t w) { return which[w].second; }, stream_of(0).seed_detector);
   pool_->run(static_cast<int>(K), [&](int wi) {
     const size_t w = static_cast<size_t>(wi);
     Stream& st = stream_of(w);
@@ -560,6 +605,7 @@ void FrontendLockstepStereo::addPairs(const uint8_t* const* left, const uint8_t*
         });
         frame->pyramid = handles[at++];
         frame->cam = rigOf(s)[static_cast<size_t>(c)].cam;
+        frame->mask = stream_masks_[static_cast<size_t>(s)][static_cast<size_t>(c)];
         frame->set_T_cam_imu(svoh::inverse(rigOf(s)[static_cast<size_t>(c)].T_B_C));
         frame->id_ = static_cast<int>(2 * st.k + static_cast<size_t>(c));
         st.bundle->frames_.push_back(frame);
@@ -976,6 +1022,14 @@ int svohs_run_sequence(svohs_engine* e, const uint8_t* base, size_t image_bytes,
       e->fe->addPairs(left.data(), right.data(), pitch, T.empty() ? nullptr : T.data(), prior.data(), has_next ? next_left.data() : nullptr, has_next ? next_right.data() : nullptr);
       if (round_ms) round_ms[k - k_first] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0;
     }
+  });
+}
+
+int svohs_set_stream_mask(svohs_engine* e, int stream, int cam, int width, int height, int pitch, const uint8_t* data)
+{
+  return svohs_guard([&] {
+    if (!e) throw std::runtime_error("svohs_set_stream_mask: NULL engine");
+    e->fe->setStreamMask(stream, cam, width, height, pitch, data);
   });
 }
 

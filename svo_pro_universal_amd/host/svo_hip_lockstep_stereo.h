@@ -23,6 +23,7 @@
 // keyframe counts as overlapping), no initialiser (the first rig pose is given), keyframes by a fixed rule.
 #pragma once
 
+#include <array>
 #include <deque>
 #include <memory>
 #include <utility>
@@ -60,6 +61,9 @@ class FrontendLockstepStereo {
   FrontendLockstepStereo(const FrontendLockstepStereo&) = delete;
   FrontendLockstepStereo& operator=(const FrontendLockstepStereo&) = delete;
   int numStreams() const { return static_cast<int>(streams_.size()); }
+  // the mask of camera c of stream s, given after construction and before the first pair (the C face: svohs_set_stream_mask); copies the image
+  void setStreamMask(int s, int c, int width, int height, int pitch, const uint8_t* data);
+  size_t masksOnDevice() const { return masks_.size(); }
   // One pair of every stream: left[s] / right[s] = level 0 of the two images (the cameras' size, `pitch` bytes per row; both NULL: stream s
   // has no pair this round).  A stream's first pair makes its first keyframes at T_imu_world_first[s].  imu_prior[s] (the array or an
   // entry may be NULL): R_imu(k)_imu(k-1) of the stream's new pair, the rotation the alignment's prior is built from.
@@ -90,6 +94,12 @@ class FrontendLockstepStereo {
   void finishSecondSeedUpdate();
   void makeKeyframes(const std::vector<std::pair<int, size_t>>& which);
   void drainReleases();
+  // the cameras' masks (io::RigCamera::mask, with the rig: shared or per stream) on the device: one upload per distinct image, released with the
+  // engine; mask_handles_[s][c] = camera c of stream s (0: none).  Both detector runs of a keyframe round take them (svoh_detect_cells_batch_masked_enqueue)
+  std::vector<std::pair<CameraMaskPtr, svoh_mask_t>> masks_;
+  std::vector<std::array<svoh_mask_t, 2>> mask_handles_;
+  std::vector<std::array<CameraMaskPtr, 2>> stream_masks_;
+  svoh_mask_t maskHandleFor(const CameraMaskPtr& m);
   const std::vector<io::RigCamera>& rigOf(int s) const { return opt_.per_stream_rig.empty() ? opt_.rig : opt_.per_stream_rig[static_cast<size_t>(s)]; }
   // one depth-filter update of the tracking streams' visible keyframes into their camera c: blocking (collected at once) or left in flight
   void seedUpdate(const std::vector<int>& trk, int c, bool leave_in_flight);

@@ -39,6 +39,9 @@ def load_host():
     lib.svohl_destroy.restype = None
     lib.svohl_add_images.argtypes = [C.c_void_p, P(C.c_void_p), C.c_int, C.c_void_p]
     lib.svohl_pose.argtypes = [C.c_void_p, C.c_int, P(capi.svoh_se3)]
+    lib.svohl_set_stream_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.svohl_masks_on_device.argtypes = [C.c_void_p, P(C.c_int)]
+    lib.svohs_set_stream_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.svohl_run_sequence.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p, C.c_void_p]
     lib.svohl_last_round.argtypes = [C.c_void_p, P(C.c_double), P(C.c_int)]
     lib.svohl_completed_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, P(C.c_int64), P(C.c_int)]
@@ -112,8 +115,10 @@ class Lockstep(object):
     then has no threads of its own; seed = its first stream's index among all groups)."""
 
     def __init__(self, ctx, n_streams, cam, T_B_C7, params_yaml, depth_min, depth_mean, depth_max, kf_every=8, n_workers=1, images_pinned=True,
-                 pool=None, seed=0, per_stream=None):
-        """per_stream (round 6): a list of n_streams dicts(params_yaml, kf_every, min_tracked, depth=(min, mean, max)) -- streams that
+                 pool=None, seed=0, per_stream=None, mask=None):
+        """mask: the camera's mask (HxW uint8 of the camera's size, 0 = never a feature here) or None; a per_stream dict may carry its own under
+        "mask" (a stream with its own "cam" takes only its own).  The engine keeps one copy per distinct mask on the device (masks_on_device).
+        per_stream (round 6): a list of n_streams dicts(params_yaml, kf_every, min_tracked, depth=(min, mean, max)) -- streams that
         differ (svohl_create_streams); missing keys take the common arguments.  If any dict has "cam" (and optionally "T_B_C7"), every stream
         gets a camera of its own (svohl_create_streams_cameras: same image size; streams without the key take `cam`; stream 0's is the engine's)."""
         self.lib = load_host()
@@ -146,6 +151,23 @@ class Lockstep(object):
             raise fe.SvohError(rc, self.lib.svohl_last_error().decode())
         self.h = h
         self._ptrs = (C.c_void_p * self.n)()
+        for s in range(self.n):
+            d = per_stream[s] if per_stream is not None else {}
+            m = d["mask"] if "mask" in d else (None if "cam" in d else mask)
+            if m is not None:
+                self.set_stream_mask(s, m)
+
+    def set_stream_mask(self, s, mask):
+        """svohl_set_stream_mask: before the stream's first frame."""
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        if m.ndim != 2:
+            raise ValueError("a mask is an HxW uint8 image")
+        self._check(self.lib.svohl_set_stream_mask(self.h, int(s), m.shape[1], m.shape[0], m.strides[0], m.ctypes.data))
+
+    def masks_on_device(self):
+        n = C.c_int()
+        self._check(self.lib.svohl_masks_on_device(self.h, C.byref(n)))
+        return n.value
 
     def _check(self, rc):
         if rc != 0:
@@ -240,7 +262,8 @@ class LockstepStereo(object):
     """One lock-step group of n_streams STEREO streams on `ctx` (host/svo_hip_lockstep_stereo.h through its C face, svohs_*)."""
     PHASES = ("pyramids", "finish seeds", "align", "reproject", "pose", "structure", "keyframes", "seed updates")
 
-    def __init__(self, ctx, n_streams, cams, T_B_C7s, params_yaml, kf_every=8, lambda_rot=0.5, n_workers=1, images_pinned=True):
+    def __init__(self, ctx, n_streams, cams, T_B_C7s, params_yaml, kf_every=8, lambda_rot=0.5, n_workers=1, images_pinned=True, masks=None):
+        """masks: (left, right) camera masks (HxW uint8, or None for a camera without one), given to every stream's rig."""
         self.lib = load_host()
         self.ctx = ctx
         self.n = int(n_streams)
@@ -252,6 +275,11 @@ class LockstepStereo(object):
         if rc != 0:
             raise fe.SvohError(rc, self.lib.svohs_last_error().decode())
         self.h = h
+        for c, m in enumerate(masks or ()):
+            if m is not None:
+                m = np.ascontiguousarray(m, dtype=np.uint8)
+                for s in range(self.n):
+                    self._check(self.lib.svohs_set_stream_mask(self.h, s, c, m.shape[1], m.shape[0], m.strides[0], m.ctypes.data))
 
     def _check(self, rc):
         if rc != 0:

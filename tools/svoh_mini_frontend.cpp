@@ -154,6 +154,9 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
     // SVOH_MINI_ALIGN_SHARED_CLASSES=1: svoh_set_align_geometry_classes(ctx, 1) -- in both modes of the tool, so that a stream alone and in lock step agree
     if (getenv("SVOH_MINI_ALIGN_SHARED_CLASSES") && svoh_set_align_geometry_classes(ctx, atoi(getenv("SVOH_MINI_ALIGN_SHARED_CLASSES")) != 0) != SVOH_OK) throw std::runtime_error(svoh_last_error_string(ctx));
     const svoh_camera& cam = rig.at(0).cam;
+    const CameraMaskPtr mask = rig[0].maskPtr();
+    // SVOH_MINI_DUMP_KEYFRAMES=1: <out_dir>/keyframes.csv, the features the detector adds at every keyframe (frame, x, y, type)
+    FILE* fk = getenv("SVOH_MINI_DUMP_KEYFRAMES") ? fopen((out_dir + "/keyframes.csv").c_str(), "w") : nullptr;
 
     params.depth_filter.use_threaded_depthfilter = false;   // the synchronous path
     SparseImgAlignHip img_align(ctx, SparseImgAlignHip::getDefaultSolverOptions(), params.img_align);
@@ -190,6 +193,7 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
       // bootstrap stand-in for the initialiser's landmarks: a keyframe's own new seeds are usable for the
       // alignment of the next frame at their current depth estimate (self reference)
       for (size_t i = n_old; i < f->num_features_; ++i) { f->seed_ref_vec_[i].keyframe = f; f->seed_ref_vec_[i].seed_id = (int)i; }
+      if (fk) for (size_t i = n_old; i < f->num_features_; ++i) fprintf(fk, "%d,%.17g,%.17g,%d\n", f->id_, f->px_vec_[2 * i], f->px_vec_[2 * i + 1], (int)f->type_vec_[i]);
       kfs.push_back(f);
       while (kfs.size() > ropt.max_n_kfs) {
         for (auto& sr : kfs.front()->seed_ref_vec_) sr.keyframe.reset();   // break the self references
@@ -243,6 +247,7 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
                              SVOH_HALFSAMPLE_REFERENCE, nullptr, &frame->pyramid) != SVOH_OK)
         throw std::runtime_error(std::string("svoh_build_pyramid: ") + svoh_last_error_string(ctx));
       frame->cam = cam;
+      frame->mask = mask;   // frame->getMask(): the calibration's mask goes with every frame into the detector
       frame->set_T_cam_imu(svoh::inverse(rig[0].T_B_C));
       frame->id_ = (int)k;
       // the previous frame's seed update: its results are needed from here on (alignment points, candidates); the wait
@@ -338,6 +343,7 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
     finish_row();
     out->wall_ms = now_ms() - wall0;
     fclose(fc);
+    if (fk) fclose(fk);
     out->n_done = n_done; out->sum_ms = sum_ms; out->n_kfs = kfs.size();
     for (const FramePtr& f : kfs) for (auto& sr : f->seed_ref_vec_) sr.keyframe.reset();
     if (last) for (auto& sr : last->seed_ref_vec_) sr.keyframe.reset();
@@ -373,7 +379,8 @@ void run_lockstep_group(const io::EurocSequence& seq, const std::vector<io::Gray
     }
     for (int lap = 0; lap < n_laps; ++lap) {
       LockstepOptions lo;
-      lo.params = params; lo.cam = rig.at(0).cam; lo.T_B_C = rig[0].T_B_C;
+      lo.params = params; lo.cam = rig.at(0).cam; lo.T_B_C = rig[0].T_B_C; lo.mask = rig[0].maskPtr();
+      lo.log_new_features = getenv("SVOH_MINI_DUMP_KEYFRAMES") != nullptr;
       lo.depth_min = depth_min; lo.depth_mean = depth_mean; lo.depth_max = depth_max; lo.kf_every = kf_every; lo.n_workers = n_workers;
       if (getenv("SVOH_MINI_MIN_TRACKED")) lo.min_tracked = (size_t)atol(getenv("SVOH_MINI_MIN_TRACKED"));
       // streams that differ (SVOH_MINI_SPEC): every stream its own parameter file, keyframe rule, first pose and walk over the images
@@ -390,7 +397,7 @@ void run_lockstep_group(const io::EurocSequence& seq, const std::vector<io::Gray
           so.min_tracked = sp.min_tracked >= 0 ? (size_t)sp.min_tracked : lo.min_tracked;
           if (!sp.calib.empty()) {
             const std::vector<io::RigCamera> own_rig = io::loadCameraRig(sp.calib);
-            so.own_camera = true; so.cam = own_rig.at(0).cam; so.T_B_C = own_rig[0].T_B_C;
+            so.own_camera = true; so.cam = own_rig.at(0).cam; so.T_B_C = own_rig[0].T_B_C; so.mask = own_rig[0].maskPtr();
           }
           lo.per_stream.push_back(so);
           if (sp.has_T0) T_first[(size_t)i] = sp.T0;
@@ -415,7 +422,7 @@ void run_lockstep_group(const io::EurocSequence& seq, const std::vector<io::Gray
       FrontendLockstep fe(ctx, n, lo);
       const bool last_lap = lap + 1 == n_laps;
       std::vector<std::unique_ptr<io::TrajectoryWriter>> traj;
-      std::vector<FILE*> csv;
+      std::vector<FILE*> csv, kf_csv;
       if (last_lap)
         for (int i = 0; i < n; ++i) {
           const int s = s0 + i;
@@ -425,17 +432,20 @@ void run_lockstep_group(const io::EurocSequence& seq, const std::vector<io::Gray
           if (!fc) throw std::runtime_error("cannot write into " + dir);
           fprintf(fc, "frame,is_kf,n_aligned,n_reprojected,n_after_pose_opt,n_seeds_updated,n_converged_seeds,ms_pyramid,ms_align,ms_reproject,ms_pose,ms_seeds,ms_kf,ms_frame,n_points_optimized,n_landmarks\n");
           csv.push_back(fc);
+          kf_csv.push_back(lo.log_new_features ? fopen((dir + "/keyframes.csv").c_str(), "w") : nullptr);
         }
       std::vector<FrontendLockstep::RoundTimes> times;
       std::vector<std::vector<size_t>> round_of((size_t)n);   // the round in which a stream's j-th frame ran
       auto write_rows = [&]() {
-        for (int i = 0; i < n; ++i)
+        for (int i = 0; i < n; ++i) {
+          if (last_lap && kf_csv[(size_t)i]) for (const FrontendLockstep::NewFeature& nf : fe.newKeyframeFeatures(i)) fprintf(kf_csv[(size_t)i], "%zu,%.17g,%.17g,%d\n", nf.k, nf.x, nf.y, nf.type);
           for (const FrontendLockstep::FrameRow& r : fe.completedRows(i)) {
             if (!last_lap) continue;
             const FrontendLockstep::RoundTimes& t = times.at(round_of[(size_t)i].at(r.k));
             fprintf(csv[(size_t)i], "%zu,%d,%zu,%zu,%zu,%zu,%zu,%.4f,%.4f,%.4f,%.4f,%.4f,%.4f,%.4f,%zu,%zu\n", r.k, (int)r.is_kf, r.n_aligned, r.n_reproj, r.n_pose, r.n_seed_upd,
                     r.n_converged, t.pyramid, t.align, t.reproject, t.pose, t.seeds, t.keyframe, t.total, r.n_struct, r.n_landmarks);
           }
+        }
       };
       std::vector<const uint8_t*> ptrs((size_t)n), next((size_t)n);
       const bool prefetch = true;
@@ -488,6 +498,7 @@ void run_lockstep_group(const io::EurocSequence& seq, const std::vector<io::Gray
         fprintf(stderr, "\n");
       }
       for (FILE* f : csv) fclose(f);
+      for (FILE* f : kf_csv) if (f) fclose(f);
     }
     (void)svoh_host_free(ctx, pinned);
     svoh_destroy(ctx);

@@ -396,6 +396,7 @@ int main(int argc, char** argv)
               row.n_lm, row.alpha, row.beta, row.ms[0], row.ms[1], row.ms[2], row.ms[3], row.ms[4], row.ms[5], row.ms[6]);
       row.valid = false;
     };
+    const CameraMaskPtr masks[2] = { rig.at(0).maskPtr(), rig.at(1).maskPtr() };   // the calibration's masks, one copy for all frames
     for (size_t k = 0; k < n_frames; ++k) {
       const double t0 = now_ms();
       const io::GrayImage img0 = io::readPngGray(seq.cam0_files[k]), img1 = io::readPngGray(seq.cam1_files[k]);
@@ -408,6 +409,7 @@ int main(int argc, char** argv)
                                SVOH_HALFSAMPLE_REFERENCE, nullptr, &frame->pyramid) != SVOH_OK)
           throw std::runtime_error(std::string("svoh_build_pyramid: ") + svoh_last_error_string(ctx));
         frame->cam = rig[(size_t)c].cam;
+        frame->mask = masks[(size_t)c];   // frame->getMask()
         frame->set_T_cam_imu(svoh::inverse(rig[(size_t)c].T_B_C));
         frame->id_ = (int)(2 * k + (size_t)c);
         bundle->frames_.push_back(frame);

@@ -35,6 +35,7 @@ int main(int argc, char** argv)
     svoh_ctx* ctx = nullptr;
     if (svoh_create(0, &ctx) != SVOH_OK) throw std::runtime_error(std::string("svoh_create: ") + svoh_last_error_string(nullptr));
     const svoh_camera& cam = rig.at(0).cam;
+    const CameraMaskPtr mask = rig[0].maskPtr();
     FeatureTrackerHip tracker(ctx, params.tracker, 1);
     tracker.setDetectors({ std::make_shared<DetectorHip>(ctx, params.detector, cam.width, cam.height) });
     FILE* ft = fopen((out_dir + "/tracks.csv").c_str(), "w");
@@ -54,6 +55,7 @@ int main(int argc, char** argv)
                              SVOH_HALFSAMPLE_REFERENCE, nullptr, &frame->pyramid) != SVOH_OK)
         throw std::runtime_error(std::string("svoh_build_pyramid: ") + svoh_last_error_string(ctx));
       frame->cam = cam;
+      frame->mask = mask;   // frame->getMask(): the new-track detection takes it
       frame->set_T_cam_imu(svoh::inverse(rig[0].T_B_C));
       frame->id_ = (int)k;
       FrameBundle::Ptr bundle(new FrameBundle);
