@@ -455,6 +455,7 @@ void load_knobs_from_env(SvohKnobs& k)
   k.align_wg_per_cu = get("SVOH_ALIGN_WG_PER_CU");
   k.kernel_timing = get("SVOH_KERNEL_TIMING");
   k.copy_kernel = get("SVOH_COPY_KERNEL");
+  k.align_side_copies = get("SVOH_ALIGN_SIDE_COPIES");
 }
 
 static int build_pyramid_levels(svoh_ctx* ctx, hipStream_t stream, const std::shared_ptr<Slab>& slab, uint8_t* base, size_t fbytes, const size_t* offs, const int* ws,
@@ -533,6 +534,11 @@ try {
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) { (void)hipStreamSynchronize(ctx->stream); }
   if (ctx->upload_stream) { (void)hipStreamSynchronize(ctx->upload_stream); }
+  // the alignment's copy stream: results of launches nobody fetched may still be on their way to h_results (a copy that was
+  // held back, svoh_internal.h, is dropped)
+  if (ctx->align_copy_stream) { (void)hipStreamSynchronize(ctx->align_copy_stream); (void)hipStreamDestroy(ctx->align_copy_stream); }
+  for (hipEvent_t ev : { ctx->ev_align_kernel[0], ctx->ev_align_kernel[1], ctx->ev_align_uploaded, ctx->ev_align_delivered })
+    if (ev) (void)hipEventDestroy(ev);
   ctx->frames.clear();
   for (auto& kv : ctx->masks) (void)hipFree(kv.second.ptr);
   ctx->masks.clear();
@@ -916,7 +922,7 @@ try {
   size_t fb = 0;
   for (const auto& kv : slabs) fb += kv.second;
   out->frame_bytes = (int64_t)fb;
-  const svoh::DevBuffer* bufs[] = { &ctx->d_desc, &ctx->d_results, &ctx->d_feat, &ctx->d_eval, &ctx->d_xchg, &ctx->d_split,
+  const svoh::DevBuffer* bufs[] = { &ctx->d_desc[0], &ctx->d_desc[1], &ctx->d_results, &ctx->d_feat, &ctx->d_eval, &ctx->d_xchg, &ctx->d_split,
                                     &ctx->d_counters, &ctx->d_unit_counts, &ctx->d_scratch0, &ctx->d_scratch1, &ctx->d_scratch2, &ctx->d_seed_bin, &ctx->d_match_seeds, &ctx->d_match_direct, &ctx->d_cand, &ctx->d_cand_multi };
   size_t wb = 0;
   for (const svoh::DevBuffer* b : bufs) wb += b->cap;

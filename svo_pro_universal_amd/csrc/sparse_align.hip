@@ -37,9 +37,58 @@
 #include "svoh_math.h"
 
 // every wait for the whole stream in this file: the alignment's staging blocks have been read (svoh_internal.h)
-#define SVOH_ALIGN_DRAIN(ctx) do { SVOH_HIP_TRY(ctx, hipStreamSynchronize((ctx)->stream)); (ctx)->align_launches_since_drain = 0; } while (0)
+// (and every copy of results that went, or still has to go, over the alignment's copy stream has arrived: align_drain)
+#define SVOH_ALIGN_DRAIN(ctx) SVOH_HIP_TRY(ctx, svoh::align_drain(ctx))
 
 namespace svoh {
+
+static hipError_t align_drain(svoh_ctx* ctx);
+
+// Side copies (svoh_internal.h): the copy stream and its events, made ONCE per context, by its first launch of the kind that can
+// take the side path.  The runtime sets a stream up, and a copy engine for each direction, when they are first used -- milliseconds
+// that belong here and not beside a kernel: the head of the launch's staged block (h, at most 1 MB of it) goes up to its device
+// block d and the same bytes come back.  Nothing in flight may read d meanwhile: launches queued ahead are waited for.
+static hipError_t align_side_setup(svoh_ctx* ctx, void* h, void* d, size_t bytes)
+{
+  if (ctx->align_copy_stream) return hipSuccess;
+  hipError_t e = ctx->align_launches_since_drain ? align_drain(ctx) : hipSuccess;
+  hipEvent_t* evs[] = { &ctx->ev_align_kernel[0], &ctx->ev_align_kernel[1], &ctx->ev_align_uploaded, &ctx->ev_align_delivered };
+  for (hipEvent_t* ev : evs)
+    if (e == hipSuccess && !*ev) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->align_copy_stream, hipStreamNonBlocking);
+  if (bytes > ((size_t)1 << 20)) bytes = (size_t)1 << 20;
+  if (e == hipSuccess) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->align_copy_stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->align_copy_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->align_copy_stream);
+  return e;
+}
+
+// the copy of a side launch's results that was held back goes onto the copy stream, behind that launch's kernel
+static hipError_t align_flush_download(svoh_ctx* ctx)
+{
+  svoh_ctx::AlignDownload& d = ctx->align_download;
+  if (!d.bytes) return hipSuccess;
+  hipError_t e = hipStreamWaitEvent(ctx->align_copy_stream, d.after, 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost, ctx->align_copy_stream);
+  if (e == hipSuccess) e = hipEventRecord(ctx->ev_align_delivered, ctx->align_copy_stream);
+  if (e != hipSuccess) return e;
+  d.bytes = 0;
+  ctx->align_delivery_pending = true;
+  return hipSuccess;
+}
+
+// every launch has run (its upload with it: the kernel waits for it) and every result is in h_results
+static hipError_t align_drain(svoh_ctx* ctx)
+{
+  hipError_t e = align_flush_download(ctx);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess && ctx->align_delivery_pending) e = hipEventSynchronize(ctx->ev_align_delivered);
+  if (e != hipSuccess) return e;
+  ctx->align_delivery_pending = false;
+  ctx->align_launches_since_drain = 0;
+  ctx->align_block_read_ev[0] = ctx->align_block_read_ev[1] = nullptr;
+  return hipSuccess;
+}
 
 struct DevCamDesc {
   DevImage ref[SVOH_MAX_LEVELS];
@@ -2222,11 +2271,15 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   PinnedBuffer& h_desc = desc_slot ? ctx->h_desc_odd : ctx->h_desc;
   if (ctx->align_launches_since_drain >= 2) {
     // this block was last read by the upload of the launch before the last one, which has not been waited for
-    if (ctx->align_staged_event_valid) SVOH_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_align_staged));
+    if (ctx->align_staged_wait_ev) SVOH_HIP_TRY(ctx, hipEventSynchronize(ctx->align_staged_wait_ev));
     else SVOH_ALIGN_DRAIN(ctx);
   }
   SVOH_HIP_TRY(ctx, h_desc.reserve(desc_bytes));
-  SVOH_HIP_TRY(ctx, ctx->d_desc.reserve(desc_bytes));
+  // the device block alternates with the pinned one: a launch queued behind another can be uploaded while that one's kernel
+  // reads the other block (below).  A block that must grow may still be read by the launch before the last one: drain first.
+  DevBuffer& d_desc = ctx->d_desc[desc_slot];
+  if (desc_bytes > d_desc.cap && ctx->align_launches_since_drain >= 1) SVOH_ALIGN_DRAIN(ctx);
+  SVOH_HIP_TRY(ctx, d_desc.reserve(desc_bytes));
   memset(static_cast<uint8_t*>(h_desc.ptr) + ctl_off, 0, 512);
   // results of launches queued since the last fetch are kept one after the other in pinned host memory -- and on the
   // device as well (a candidate projection queued behind several launches reads the result of any of them):
@@ -2234,7 +2287,12 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   const bool delivers = (S == 1 || cluster) && eval_level < 0;
   const size_t dev_results_off = delivers ? ctx->align_pending_dev : 0;
   {
-    const size_t need = sizeof(svoh_align_result) * (dev_results_off + (size_t)n_desc + n_problems);
+    // (as for h_results below: the first launch of a queue makes room for a queue of launches of its size, so that the
+    // launches behind it do not drain the stream here to replace the block)
+    size_t want_dev = dev_results_off + (size_t)n_desc + n_problems;
+    if (delivers && dev_results_off == 0 && (size_t)svoh_ctx::kAlignEventRing * (size_t)n_problems <= svoh_ctx::kMaxQueuedResults)
+      want_dev *= (size_t)svoh_ctx::kAlignEventRing;
+    const size_t need = sizeof(svoh_align_result) * want_dev;
     if (need > ctx->d_results.cap) {
       if (dev_results_off) {   // earlier launches' results live in the old block: let them finish, take them along
         SVOH_ALIGN_DRAIN(ctx);
@@ -2276,7 +2334,7 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   DevProblemDesc* hp = static_cast<DevProblemDesc*>(h_desc.ptr);
   DevCamDesc* hc = reinterpret_cast<DevCamDesc*>(hp + n_desc);
   uint8_t* hup = static_cast<uint8_t*>(h_desc.ptr) + up_base;
-  uint8_t* dup = static_cast<uint8_t*>(ctx->d_desc.ptr) + up_base;
+  uint8_t* dup = static_cast<uint8_t*>(d_desc.ptr) + up_base;
   size_t up_off = 0;
   int cam_idx = 0, feat_off = 0;
   const int need_levels = opt->max_level + 1;
@@ -2363,21 +2421,66 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
     pos_jobs_device = reinterpret_cast<const PosFromSeedsJob*>(dup + up_off);
     up_off += (sizeof(PosFromSeedsJob) * pos_jobs.size() + 63) & ~(size_t)63;
   }
-  SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, ctx->d_desc.ptr, h_desc.ptr, up_base + up_off));
+  // Side copies (svoh_internal.h): a launch of the batch geometry queued behind an alignment launch that is still in flight
+  // sends its block up on the copy stream, beside that launch's kernel, and its results down beside the next one's.  Every
+  // other launch -- the first of a queue, small ones, keyed ones (a lock-step group: four groups share the hardware queues,
+  // a side stream costs them more than it gives), evaluation, split -- keeps its copies on the context's stream.
+  // The copy stream is made by the context's first launch of this kind, queued or not: a caller's first such launches are
+  // its warm-up, and the runtime's set-up of a stream and its copy engines takes milliseconds (align_side_setup).
+  // By default only a block larger than the copy kernels' window (1 MB, copy_by_kernel in context.hip) goes there: a smaller one
+  // travels by copy kernel on the context's stream with no hand-over to a copy engine at all, and the side path costs it more than
+  // it saves (1024 frame pairs per step, 0.9 MB: 1.38 ms per step with side copies against 1.20 without,
+  // profiles/r07_align_side_copies_ab.txt).  SVOH_ALIGN_SIDE_COPIES=1 sends every such launch there, =0 none.
+  const int side_knob = ctx->knobs.align_side_copies;
+  const bool side_kind = n_desc >= ctx->num_cus && !cluster && !split && !forced && eval_level < 0 &&
+                         (side_knob == kKnobUnset ? up_base + up_off > ((size_t)1 << 20) : side_knob != 0);
+  if (side_kind) SVOH_HIP_TRY(ctx, align_side_setup(ctx, h_desc.ptr, d_desc.ptr, up_base + up_off));
+  const bool side = side_kind && ctx->align_launches_since_drain >= 1;
+  const unsigned prev_slot = desc_slot ^ 1u;
+  if (side) {
+    // what this launch does not read must not wait behind it: the launch before this one, if it kept to the context's stream,
+    // has no event behind its kernel yet (the launch after this one will upload into its block)
+    if (!ctx->align_block_read_ev[prev_slot]) {
+      SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_kernel[prev_slot], ctx->stream));
+      ctx->align_block_read_ev[prev_slot] = ctx->ev_align_kernel[prev_slot];
+    }
+    // the kernel of the launch before the last one may still read this device block
+    if (ctx->align_block_read_ev[desc_slot]) SVOH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->align_copy_stream, ctx->align_block_read_ev[desc_slot], 0));
+    SVOH_HIP_TRY(ctx, hipMemcpyAsync(d_desc.ptr, h_desc.ptr, up_base + up_off, hipMemcpyHostToDevice, ctx->align_copy_stream));
+    SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_uploaded, ctx->align_copy_stream));
+    // what the host waits for before it writes the OTHER pinned block again lies behind the upload that last read that block,
+    // the previous launch's: on the copy stream if it went there, else behind that launch's kernel on the context's stream
+    if (ctx->align_last_was_side) {
+      SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_staged, ctx->align_copy_stream));
+      ctx->align_staged_wait_ev = ctx->ev_align_staged;
+    } else {
+      ctx->align_staged_wait_ev = ctx->align_block_read_ev[prev_slot];
+    }
+    SVOH_HIP_TRY(ctx, align_flush_download(ctx));   // the previous launch's results: behind this upload, beside this kernel
+    SVOH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_align_uploaded, 0));
+    ++ctx->align_side_launches;
+  } else {
+    SVOH_HIP_TRY(ctx, align_flush_download(ctx));
+    SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d_desc.ptr, h_desc.ptr, up_base + up_off));
+  }
   if (pos_jobs_device) {
     const int rcp = svoh_launch_pos_from_seed_batch(ctx, (int)pos_jobs.size(), pos_jobs_max_n, pos_jobs_device);
     if (rcp != SVOH_OK) return rcp;
   }
   ctx->align_desc_slot = desc_slot;
-  ctx->align_staged_event_valid = false;
-  if (ctx->align_launches_since_drain >= 1) {   // queued behind a launch nobody has waited for: the next one may need this
-    SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_staged, ctx->stream));
-    ctx->align_staged_event_valid = true;
+  if (!side) {
+    ctx->align_staged_wait_ev = nullptr;
+    if (ctx->align_launches_since_drain >= 1) {   // queued behind a launch nobody has waited for: the next one may need this
+      SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_staged, ctx->stream));
+      ctx->align_staged_wait_ev = ctx->ev_align_staged;
+    }
+    ctx->align_block_read_ev[desc_slot] = nullptr;   // (an event of an earlier kernel on this block says nothing about this one)
   }
+  ctx->align_last_was_side = side;
   ++ctx->align_launches_since_drain;
 
   AlignKernelArgs args;
-  args.problems = static_cast<const DevProblemDesc*>(ctx->d_desc.ptr);
+  args.problems = static_cast<const DevProblemDesc*>(d_desc.ptr);
   args.cams = reinterpret_cast<const DevCamDesc*>(args.problems + n_desc);
   args.results = static_cast<svoh_align_result*>(ctx->d_results.ptr) + dev_results_off;
   double* w = static_cast<double*>(ctx->d_feat.ptr);
@@ -2403,7 +2506,7 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
     SVOH_HIP_TRY(ctx, ctx->d_xchg.reserve(xchg_bytes));
     args.cluster = S;
     args.xchg = static_cast<double*>(ctx->d_xchg.ptr);
-    args.bar = reinterpret_cast<unsigned int*>(static_cast<uint8_t*>(ctx->d_desc.ptr) + ctl_off + 256);   // zero, as above
+    args.bar = reinterpret_cast<unsigned int*>(static_cast<uint8_t*>(d_desc.ptr) + ctl_off + 256);   // zero, as above
   }
   if (split && !split->update) {
     args.ext_state = split->ext_state;
@@ -2424,7 +2527,7 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
     if (eu != hipSuccess) return set_error(ctx, SVOH_ERR_HIP, "gn_update launch failed: %s", hipGetErrorString(eu));
     return SVOH_OK;
   }
-  args.queue = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(ctx->d_desc.ptr) + ctl_off);   // zero: uploaded with the descriptors
+  args.queue = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(d_desc.ptr) + ctl_off);   // zero: uploaded with the descriptors
 #ifdef SVOH_PHASE_STAMPS
   SVOH_HIP_TRY(ctx, ctx->d_scratch0.reserve(sizeof(long long) * 20 * (size_t)n_problems));
   args.stamps = static_cast<long long*>(ctx->d_scratch0.ptr);
@@ -2492,9 +2595,20 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   }
   // the results follow the kernel to pinned host memory right away, so that a caller which queues several
   // launches and fetches once still has every launch's output delivered
+  if (side) {
+    // behind this kernel: the copy stream may write this device block again (the launch after the next), and take the results
+    SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_kernel[desc_slot], ctx->stream));
+    ctx->align_block_read_ev[desc_slot] = ctx->ev_align_kernel[desc_slot];
+    // held back until the next launch has queued its upload, or somebody drains (align_flush_download)
+    ctx->align_download.dst = static_cast<svoh_align_result*>(ctx->h_results.ptr) + ctx->align_pending_results;
+    ctx->align_download.src = args.results;
+    ctx->align_download.bytes = sizeof(svoh_align_result) * n_problems;
+    ctx->align_download.after = ctx->ev_align_kernel[desc_slot];
+  }
   if (delivers) {   // cluster: entry 0 is share 0's copy of the common result
-    SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, static_cast<svoh_align_result*>(ctx->h_results.ptr) + ctx->align_pending_results,
-                                        args.results, sizeof(svoh_align_result) * n_problems));
+    if (!side)
+      SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, static_cast<svoh_align_result*>(ctx->h_results.ptr) + ctx->align_pending_results,
+                                          args.results, sizeof(svoh_align_result) * n_problems));
     ctx->align_last_results_off = ctx->align_pending_results;
     // where on the device result #k of the queue lives (svoh_project_candidates_enqueue's align_result_index)
     if (ctx->align_pending_results == 0) ctx->align_result_dev_index.clear();
@@ -2536,6 +2650,11 @@ int svoh_sparse_align_enqueue(svoh_ctx* ctx, const svoh_align_options* options, 
 try {
   return enqueue_align(ctx, options, n_problems, problems, -1);
 } SVOH_ABI_CATCH(ctx)
+
+#ifdef SVOH_TEST_HOOKS
+// libsvo_hip_testhooks.so only (not part of include/svo_hip.h): how many launches of this context took the side path
+unsigned long long svoh_test_align_side_launches(const svoh_ctx* ctx) { return ctx ? ctx->align_side_launches : 0; }
+#endif
 
 int svoh_sparse_align_geometry_key(svoh_ctx* ctx, const svoh_align_options* options, const svoh_align_problem* problem, int32_t* key)
 try {

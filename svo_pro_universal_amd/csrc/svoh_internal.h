@@ -193,9 +193,9 @@ struct SvohKnobs {
   int seed_binning = kKnobUnset;              // SVOH_SEED_BINNING: 0 = no spatial binning of large seed batches
   int pose_threads = kKnobUnset;              // SVOH_POSE_THREADS: 64 / 256 / 512
   int align_cluster = kKnobUnset;             // SVOH_ALIGN_CLUSTER: workgroups per problem (0 = never)
-#ifdef SVOH_TEST_HOOKS
+  // (a member of every build: libsvo_hip_testhooks.so links translation units compiled with and without SVOH_TEST_HOOKS, and all
+  // of them must agree on where the members behind this one lie; only the test-hook build ever sets or reads it)
   int align_cluster_test_absent = kKnobUnset; // SVOH_ALIGN_CLUSTER_TEST_ABSENT: a partner that never arrives (libsvo_hip_testhooks.so only)
-#endif
   int align_threads = kKnobUnset;             // SVOH_ALIGN_THREADS: 256 / 512 (anything else = 256)
   int align_rows = kKnobUnset;                // SVOH_ALIGN_ROWS: lanes per patch of the alignment's 512-thread geometry: 2, 4 or 8 (<= patch size); anything else = a lane per patch
   int align_latency_build = kKnobUnset;       // SVOH_ALIGN_LATENCY_BUILD: 0 = small launches use the batch build of the 256-thread kernel too
@@ -203,6 +203,7 @@ struct SvohKnobs {
   int align_wg_per_cu = kKnobUnset;           // SVOH_ALIGN_WG_PER_CU
   int kernel_timing = kKnobUnset;             // SVOH_KERNEL_TIMING: 1 = bracket every kernel with an event pair (svoh_set_kernel_timing)
   int copy_kernel = kKnobUnset;               // SVOH_COPY_KERNEL / svoh_set_copy_policy: 0 = staged blocks through hipMemcpyAsync, 1 (default) = copy kernels for 16 KB .. 1 MB, 2 = copy kernels always
+  int align_side_copies = kKnobUnset;         // SVOH_ALIGN_SIDE_COPIES: 0 = a queued batch launch of the alignment keeps its copies on the context's stream (A/B), 1 = every one takes the copy stream; unset = those whose block is larger than 1 MB
   static int or_default(int v, int dflt) { return v == kKnobUnset ? dflt : v; }
 };
 void load_knobs_from_env(SvohKnobs& k);
@@ -230,7 +231,7 @@ struct svoh_ctx {
   hipEvent_t ev_features = nullptr;     // ... and what says its last copy has run (made at first use)
 
   // sparse-align workspaces
-  svoh::DevBuffer d_desc;      // problem + camera descriptors
+  svoh::DevBuffer d_desc[2];   // problem + camera descriptors, control words, uploaded feature arrays: the block of even launches and of odd ones (align_desc_slot)
   svoh::DevBuffer d_results;   // svoh_align_result[n]
   svoh::DevBuffer d_feat;      // per-feature workspace
   svoh::DevBuffer d_eval;      // evaluate() outputs
@@ -261,9 +262,24 @@ struct svoh_ctx {
   // each records ev_align_staged behind its upload, and the third and later wait for the event of the launch before them
   // -- which lies behind the upload that last read their block.
   hipEvent_t ev_align_staged = nullptr;
-  bool align_staged_event_valid = false;      // ev_align_staged was recorded by the most recent launch
+  hipEvent_t align_staged_wait_ev = nullptr;  // what the most recent launch recorded behind the upload of the launch before it (ev_align_staged, or see below); nullptr: nothing
   unsigned align_launches_since_drain = 0;    // alignment launches queued since this file last waited for the stream
   unsigned align_desc_slot = 0;
+  // Side copies (sparse_align.hip, enqueue_align; SVOH_ALIGN_SIDE_COPIES=0 turns them off).  A batch launch queued behind an
+  // alignment launch that nobody has waited for uploads its block on align_copy_stream while that launch's kernel runs -- into the
+  // device block the kernel is not reading -- and its results travel to h_results on the same stream while the NEXT kernel runs:
+  //   copy stream:  wait(kernel N-2 done)  upload N  record(ev_align_uploaded)  record(ev_align_staged)  wait(kernel N-1 done)  results N-1  record(ev_align_delivered)
+  //   ctx->stream:  wait(ev_align_uploaded)  kernel N  record(ev_align_kernel[slot])
+  // The copy of launch N's results is held back (align_download) until the next launch has put its upload on the copy stream --
+  // behind a wait for kernel N that upload would not run beside kernel N -- or until somebody drains (align_drain).
+  hipStream_t align_copy_stream = nullptr;    // made by the context's first launch of the batch geometry (align_side_setup), never by a context of small or keyed launches
+  hipEvent_t ev_align_kernel[2] = {};         // on ctx->stream behind a kernel that read d_desc[slot] (a side launch records its own; the launch behind an in-stream one records that one's)
+  hipEvent_t align_block_read_ev[2] = {};     // the event behind the last kernel that read d_desc[slot], if one was recorded since the last drain
+  hipEvent_t ev_align_uploaded = nullptr, ev_align_delivered = nullptr;
+  struct AlignDownload { void* dst = nullptr; const void* src = nullptr; size_t bytes = 0; hipEvent_t after = nullptr; } align_download;   // bytes == 0: none held back
+  bool align_delivery_pending = false;        // ev_align_delivered lies behind copies to h_results that nobody has waited for
+  bool align_last_was_side = false;           // the most recent launch uploaded on the copy stream
+  unsigned long long align_side_launches = 0; // launches that took the side path (read by svoh_test_align_side_launches of libsvo_hip_testhooks.so only)
   bool align_shared_classes = false;   // svoh_set_align_geometry_classes
   bool align_no_cluster = false;   // svoh_sparse_align_batch repeating a launch whose cluster gave up
   hipEvent_t ev_misc_start = nullptr, ev_misc_stop = nullptr;  // KLT / matcher / seeds
