@@ -367,6 +367,15 @@ int svoh_sparse_align_kernel_ms_history(svoh_ctx* ctx, int n, float* ms, int* n_
  * that must KNOW which instantiation they measured instead of inferring it from the launch rule. */
 int svoh_sparse_align_last_launch_info(svoh_ctx* ctx, int32_t* geometry_key, int32_t* grid, int32_t* n_desc);
 
+/* The LDS bytes the kernel of that same launch had for the levels' images (after the workspace rows and, in the
+ * two-workgroups-per-CU geometry, the instantiation's static LDS were taken off).  With it a caller can tell which way every
+ * level's images took: from the coarsest level down, a level whose images (every camera's reference and current image, each
+ * rounded up to 16 bytes) still fit BESIDE the coarser ones is resident from the problem's start; a finer one that fits by
+ * itself is staged alone when its turn comes; the rest is read from global memory.  Host-side bookkeeping, no
+ * synchronisation; fails before the first full-run launch.  (A level built with SVOH_HALFSAMPLE_SSE2 forced on a width that
+ * is no multiple of 16 keeps its last columns unwritten, on the device as in the reference: not a case of this query.) */
+int svoh_sparse_align_last_launch_lds(svoh_ctx* ctx, int32_t* lds_img_bytes);
+
 /* Diagnostic/parity entry: evaluate H (8x8 col-major), g (8), chi2, n_meas for
  * ONE problem at a given level and state, i.e. SparseImgAlign::evaluateError
  * (sparse_img_align.cpp:115-156) on a fresh level.  visibility (may be NULL)

@@ -1964,7 +1964,7 @@ struct LaunchCfg { int nt; size_t lds; };
 
 constexpr size_t kLdsPerCu = 163840;   // gfx950: 160 KB per compute unit
 template <int P, int NT, bool ILLUM, bool CLUSTER, bool ROBUST, int LPP = 1, bool LAT = false, bool RIG = false>
-static hipError_t launch_one(hipStream_t st, int grid, size_t lds, AlignKernelArgs args)
+static hipError_t launch_one(hipStream_t st, int grid, size_t lds, AlignKernelArgs args, int32_t* lds_img_launched)
 {
   auto kern = sparse_align_kernel<P, NT, ILLUM, CLUSTER, ROBUST, LPP, LAT, RIG>;
   if (NT == 256 && args.lds_two_per_cu) {
@@ -1991,26 +1991,27 @@ static hipError_t launch_one(hipStream_t st, int grid, size_t lds, AlignKernelAr
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
+  *lds_img_launched = args.lds_img_bytes;   // what the kernel decides the levels' residency with (svoh_sparse_align_last_launch_lds)
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, args);
   return hipGetLastError();
 }
 
 // lpp: lanes per patch (1: a lane owns a patch; 2, 4, 8 <= P: the rows geometry, 512 threads)
 template <int P, bool ILLUM, bool ROBUST>
-static hipError_t launch_nt(hipStream_t st, int nt, int lpp, int grid, size_t lds, const AlignKernelArgs& args)
+static hipError_t launch_nt(hipStream_t st, int nt, int lpp, int grid, size_t lds, const AlignKernelArgs& args, int32_t* lds_img_launched)
 {
-  if (args.cluster > 1) return launch_one<P, 256, ILLUM, true, ROBUST>(st, grid, lds, args);
+  if (args.cluster > 1) return launch_one<P, 256, ILLUM, true, ROBUST>(st, grid, lds, args, lds_img_launched);
   if (nt == 256) {
-    if (args.latency_build) return args.rig_build ? launch_one<P, 256, ILLUM, false, ROBUST, 1, true, true>(st, grid, lds, args)
-                                                  : launch_one<P, 256, ILLUM, false, ROBUST, 1, true>(st, grid, lds, args);
-    return launch_one<P, 256, ILLUM, false, ROBUST>(st, grid, lds, args);
+    if (args.latency_build) return args.rig_build ? launch_one<P, 256, ILLUM, false, ROBUST, 1, true, true>(st, grid, lds, args, lds_img_launched)
+                                                  : launch_one<P, 256, ILLUM, false, ROBUST, 1, true>(st, grid, lds, args, lds_img_launched);
+    return launch_one<P, 256, ILLUM, false, ROBUST>(st, grid, lds, args, lds_img_launched);
   }
-  if (lpp <= 1 && args.rig_build) return launch_one<P, 512, ILLUM, false, ROBUST, 1, false, true>(st, grid, lds, args);
+  if (lpp <= 1 && args.rig_build) return launch_one<P, 512, ILLUM, false, ROBUST, 1, false, true>(st, grid, lds, args, lds_img_launched);
   switch (lpp) {
-    case 2: return launch_one<P, 512, ILLUM, false, ROBUST, 2>(st, grid, lds, args);
-    case 4: return launch_one<P, 512, ILLUM, false, ROBUST, 4>(st, grid, lds, args);
-    case 8: if constexpr (P == 8) return launch_one<P, 512, ILLUM, false, ROBUST, 8>(st, grid, lds, args);
-    default: return launch_one<P, 512, ILLUM, false, ROBUST>(st, grid, lds, args);
+    case 2: return launch_one<P, 512, ILLUM, false, ROBUST, 2>(st, grid, lds, args, lds_img_launched);
+    case 4: return launch_one<P, 512, ILLUM, false, ROBUST, 4>(st, grid, lds, args, lds_img_launched);
+    case 8: if constexpr (P == 8) return launch_one<P, 512, ILLUM, false, ROBUST, 8>(st, grid, lds, args, lds_img_launched);
+    default: return launch_one<P, 512, ILLUM, false, ROBUST>(st, grid, lds, args, lds_img_launched);
   }
 }
 
@@ -2566,17 +2567,18 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   const int ev_slot = (int)(ctx->align_timed_launches % svoh_ctx::kAlignEventRing);
   if (timed) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_start[ev_slot], ctx->stream));
   const bool robust = opt->robustification != 0;
+  int32_t lds_img_launched = 0;
 #ifdef SVOH_DEV_ONLY_PLAIN   // development builds only (scripts/kernel_resources.sh, quick A/B libraries): the 4x4 / 8x8 kernels without illumination terms and robust weights
   if (robust || illum) return set_error(ctx, SVOH_ERR_UNSUPPORTED, "development build: plain kernels only");
-  e = opt->patch_size == 4 ? launch_nt<4, false, false>(ctx->stream, nt, rows, grid, lds, args)
-                           : launch_nt<8, false, false>(ctx->stream, nt, rows, grid, lds, args);
+  e = opt->patch_size == 4 ? launch_nt<4, false, false>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched)
+                           : launch_nt<8, false, false>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched);
 #else
   if (opt->patch_size == 4) {
-    if (robust) e = illum ? launch_nt<4, true, true>(ctx->stream, nt, rows, grid, lds, args) : launch_nt<4, false, true>(ctx->stream, nt, rows, grid, lds, args);
-    else e = illum ? launch_nt<4, true, false>(ctx->stream, nt, rows, grid, lds, args) : launch_nt<4, false, false>(ctx->stream, nt, rows, grid, lds, args);
+    if (robust) e = illum ? launch_nt<4, true, true>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched) : launch_nt<4, false, true>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched);
+    else e = illum ? launch_nt<4, true, false>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched) : launch_nt<4, false, false>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched);
   } else {
-    if (robust) e = illum ? launch_nt<8, true, true>(ctx->stream, nt, rows, grid, lds, args) : launch_nt<8, false, true>(ctx->stream, nt, rows, grid, lds, args);
-    else e = illum ? launch_nt<8, true, false>(ctx->stream, nt, rows, grid, lds, args) : launch_nt<8, false, false>(ctx->stream, nt, rows, grid, lds, args);
+    if (robust) e = illum ? launch_nt<8, true, true>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched) : launch_nt<8, false, true>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched);
+    else e = illum ? launch_nt<8, true, false>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched) : launch_nt<8, false, false>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched);
   }
 #endif
   if (e != hipSuccess)
@@ -2592,6 +2594,7 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   ++ctx->align_launches;
   if (!split && eval_level < 0) {   // svoh_sparse_align_last_launch_info
     ctx->align_last_geometry_key = geo.key(); ctx->align_last_grid = grid; ctx->align_last_n_desc = n_desc;
+    ctx->align_last_lds_img_bytes = lds_img_launched;
   }
   // the results follow the kernel to pinned host memory right away, so that a caller which queues several
   // launches and fetches once still has every launch's output delivered
@@ -2766,6 +2769,15 @@ try {
   SVOH_REQUIRE(ctx, geometry_key && grid && n_desc, "NULL argument");
   SVOH_REQUIRE(ctx, ctx->align_last_geometry_key != 0, "no full-run alignment launch on this context yet");
   *geometry_key = ctx->align_last_geometry_key; *grid = ctx->align_last_grid; *n_desc = ctx->align_last_n_desc;
+  return SVOH_OK;
+} SVOH_ABI_CATCH(ctx)
+
+int svoh_sparse_align_last_launch_lds(svoh_ctx* ctx, int32_t* lds_img_bytes)
+try {
+  if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  SVOH_REQUIRE(ctx, lds_img_bytes, "NULL argument");
+  SVOH_REQUIRE(ctx, ctx->align_last_geometry_key != 0, "no full-run alignment launch on this context yet");
+  *lds_img_bytes = ctx->align_last_lds_img_bytes;
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
 

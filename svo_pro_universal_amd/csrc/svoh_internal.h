@@ -256,6 +256,7 @@ struct svoh_ctx {
   unsigned long long align_launches = 0;
   // what the most recent full-run alignment launch looked like (svoh_sparse_align_last_launch_info); key 0: none yet
   int32_t align_last_geometry_key = 0, align_last_grid = 0, align_last_n_desc = 0;
+  int32_t align_last_lds_img_bytes = 0;   // ... and the LDS bytes its kernel had for the levels' images (svoh_sparse_align_last_launch_lds)
   // The pinned staging blocks are reused.  A launch fetched before the next one is queued (the per-frame use) has
   // drained the stream: nothing to protect, no event on the stream (an event record costs a launch 4.5 us of stream time,
   // tools/svoh_call_overhead).  Launches queued back to back alternate between the two blocks; from the second one on

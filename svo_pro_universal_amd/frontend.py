@@ -207,6 +207,12 @@ class Context(object):
         return dict(key=k, cluster_g=k & 0xff, nt=512 if (k >> 8) & 1 else 256, rows=(k >> 9) & 0xf,
                     latency=bool((k >> 13) & 1), rig=bool((k >> 14) & 1), grid=grid.value, n_desc=n_desc.value)
 
+    def last_align_launch_lds(self):
+        """svoh_sparse_align_last_launch_lds: the LDS bytes the most recent full-run alignment launch had for the levels' images."""
+        n = C.c_int32()
+        self._check(self.lib.svoh_sparse_align_last_launch_lds(self.h, C.byref(n)))
+        return n.value
+
     def sparse_align_evaluate(self, opt, problem, level):
         H = np.zeros(64)
         g = np.zeros(8)
