@@ -91,7 +91,9 @@ typedef enum svoh_distortion {
   SVOH_DISTORTION_RADTAN = 1,       /* vk::cameras::RadialTangentialDistortion k1 k2 p1 p2 */
   SVOH_DISTORTION_EQUIDISTANT = 2,  /* vk::cameras::EquidistantDistortion k1 k2 k3 k4 (Kannala-Brandt; YAML "equidistant") */
   SVOH_DISTORTION_ATAN = 3          /* vk::cameras::AtanDistortion s (the FOV model; YAML "fisheye").  The reference has no
-                                     * Jacobian for it: every entry that would evaluate one returns SVOH_ERR_UNSUPPORTED */
+                                     * Jacobian for it: every entry that would evaluate one returns SVOH_ERR_UNSUPPORTED
+                                     * (svoh_camera_maths with J, svoh_optimize_pose_batch* as described there); the
+                                     * candidate projection evaluates none and runs it */
 } svoh_distortion;
 
 /* vk::cameras::PinholeProjection<Distortion>
@@ -659,7 +661,13 @@ int svoh_matcher_deferred_set_cur_frame(svoh_ctx* ctx, const svoh_frame_view* cu
  * (sparse_img_align.cpp:100-107), so that one svoh_sparse_align_fetch delivers the pose AND the candidates of the
  * frame: the candidate projection costs no round trip of its own.  With align_result_index < 0 the first pose argument
  * is T_f_w itself.  collect copies the results out (n must be the queued call's n).  Host pointers; one queued call
- * at a time. */
+ * at a time.
+ *
+ * Camera models: all four.  NONE | RADTAN run the kernel they always ran; an EQUIDISTANT or ATAN camera runs its wide
+ * twin (no Jacobian is evaluated, so ATAN is accepted).  Frame::isVisible's cone is back_project3 of pixel (0, 0),
+ * normalised, for every model.  For the wide models the pixels are the host mirror's to rounding, not to the bit (the
+ * device's atan / tan are not libm's).  An ATAN camera whose s = d[0] is zero or not finite, or a distortion value
+ * outside svoh_distortion, is SVOH_ERR_INVALID_ARGUMENT (as in svoh_camera_maths); the staged entries check every job. */
 int svoh_project_candidates_enqueue(svoh_ctx* ctx, const svoh_camera* cam, const svoh_se3* T_f_w_or_T_cam_imu,
                                     const svoh_se3* T_imu_world_ref, int align_result_index, int n_kf,
                                     const svoh_se3* T_world_kf, int n, const uint8_t* kind, const int32_t* kf,
@@ -715,6 +723,8 @@ typedef struct svoh_candidate_stage_t {
 } svoh_candidate_stage_t;
 int svoh_project_candidates_stage(svoh_ctx* ctx, int n_jobs, int n_kf_total, int n_points_total, svoh_candidate_stage_t* out);
 int svoh_project_candidates_stage_ranges(svoh_ctx* ctx, int n_jobs, int n_kf_total, int n_points_total, svoh_candidate_stage_t* out);
+/* Camera models: as svoh_project_candidates; one launch serves every job, and it runs the wide twin if any job's camera
+ * is EQUIDISTANT or ATAN (a NONE | RADTAN job beside it then agrees with the single entry to rounding). */
 int svoh_project_candidates_enqueue_staged(svoh_ctx* ctx);
 int svoh_project_candidates_enqueue_staged_units(svoh_ctx* ctx);   /* the ranges form with mu_unit entries >= 0 */
 int svoh_project_candidates_wait(svoh_ctx* ctx);
@@ -979,7 +989,17 @@ typedef struct svoh_pose_result {
 
 /* Replaces PoseOptimizer::run (src/svo/src/pose_optimizer.cpp:39-113) for n_problems frame bundles at once:
  * start errors -> MAD scale, Gauss-Newton on T_imu_world with Tukey weights (and the optional rotation prior),
- * removeOutliers.  run()'s return value is n_meas - n_deleted_edges - n_deleted_corners.  Host pointers. */
+ * removeOutliers.  run()'s return value is n_meas - n_deleted_edges - n_deleted_corners.  Host pointers.
+ *
+ * Camera models (all three entries).  A launch whose error type evaluates the camera (IMAGE_PLANE, BEARING_DIFF) and in
+ * which at least one camera of any problem is EQUIDISTANT or ATAN runs the wide build of the kernel; every other
+ * launch -- UNIT_PLANE uses f and the point only -- runs the narrow one, whatever the models.  ATAN has no Jacobian in
+ * the reference: it is accepted with UNIT_PLANE, and with BEARING_DIFF through the host-array entries while no usable
+ * feature of that camera has an edgelet type.  It is refused with SVOH_ERR_UNSUPPORTED, before anything is staged or
+ * launched and with the context left usable: with IMAGE_PLANE; with BEARING_DIFF and a usable edgelet; with
+ * BEARING_DIFF through svoh_optimize_pose_batch_packed, whose types live on the device and cannot be checked.
+ * An ATAN camera whose s = d[0] is zero or not finite is SVOH_ERR_INVALID_ARGUMENT with every error type, as in
+ * svoh_camera_maths (1 / s is part of the model); so is a distortion value outside svoh_distortion. */
 int svoh_optimize_pose_batch(svoh_ctx* ctx, const svoh_pose_options* options, int n_problems,
                              const svoh_pose_problem* problems, svoh_pose_result* results);
 /* The same call with a hook: after the launch and the copy of its results have been queued, `after_launch(user)` runs on

@@ -3316,8 +3316,14 @@ static int run_epipolar(svoh_ctx* ctx, const svoh_matcher_options* mopt, int n_r
 // truncated pixel.  The current frame's pose is given, or composed on the device from the alignment result that
 // the launch queued in front of this one has left in device memory (T_f_w = T_cam_imu * T_icur_iref * T_imu_world of
 // the reference frame: sparse_img_align.cpp:100-107), so that the projection needs no round trip of its own.
-// This file is compiled without FMA contraction and the maths is the host mirror's (svoh_math.h): same bits as
-// reprojector_utils::getCandidate of the host layer.
+// This file is compiled without FMA contraction and the maths is the host mirror's (svoh_math.h): for the narrow
+// cameras (NONE | RADTAN) the same bits as reprojector_utils::getCandidate of the host layer.  For EQUIDISTANT and ATAN
+// that does NOT hold: the device's atan / tan come from ocml, the host's from libm, and the two may round a double
+// differently -- pixels agree to rounding, and a point on the image box or on the 8-pixel margin can fall on either
+// side.  The lock-step engines' byte-identity claims rest on the sentence above and cover the narrow family only: an
+// open point for whoever brings the image kernels to the wide cameras.
+// Each kernel is a body templated on the camera type with two __global__ names: the old one for CamModel and a
+// *_wide_kernel twin for CamModelWide, which evaluates every model.
 struct CandidateArgs {
   svoh_camera cam;
   svoh_se3 T_a;                       // T_f_w of the current frame, or T_cam_imu of it when `align_result` is set
@@ -3333,13 +3339,14 @@ struct CandidateArgs {
   int n, n_kf;
 };
 
-__global__ __launch_bounds__(256) void project_candidates_kernel(const CandidateArgs a)
+template <class Cam>
+__device__ __forceinline__ void project_candidates_body(const CandidateArgs& a)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= a.n) return;
   Rigid T_f_w = load_rigid(a.T_a);
   if (a.align_result) T_f_w = mul(mul(T_f_w, load_rigid(a.align_result->T_icur_iref)), load_rigid(a.T_b));
-  const CamModel cm = load_camera(a.cam);
+  const Cam cm = load_camera_as<Cam>(a.cam);
   Vec3 xyz = { a.v[3 * i], a.v[3 * i + 1], a.v[3 * i + 2] };
   bool ok = true;
   if (a.kind[i]) {
@@ -3372,6 +3379,10 @@ __global__ __launch_bounds__(256) void project_candidates_kernel(const Candidate
   a.visible[i] = ok ? 1 : 0;
 }
 
+// the narrow family (NONE | RADTAN) under the name it always had, and the twin for launches with an EQUIDISTANT or ATAN camera
+__global__ __launch_bounds__(256) void project_candidates_kernel(const CandidateArgs a) { project_candidates_body<CamModel>(a); }
+__global__ __launch_bounds__(256) void project_candidates_wide_kernel(const CandidateArgs a) { project_candidates_body<CamModelWide>(a); }
+
 static int enqueue_candidates(svoh_ctx* ctx, const svoh_camera* cam, const svoh_se3* T_a, const svoh_se3* T_b, int align_result_index,
                               int n_kf, const svoh_se3* T_world_kf, int n, const uint8_t* kind, const int32_t* kf, const double* v,
                               const double* mu)
@@ -3379,7 +3390,9 @@ static int enqueue_candidates(svoh_ctx* ctx, const svoh_camera* cam, const svoh_
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, cam && T_a && n >= 1 && n <= (1 << 22) && kind && kf && v && mu, "bad arguments");
   SVOH_REQUIRE(ctx, n_kf >= 0 && n_kf <= 4096 && (n_kf == 0 || T_world_kf), "bad keyframe table");
-  SVOH_REQUIRE(ctx, cam->distortion == SVOH_DISTORTION_NONE || cam->distortion == SVOH_DISTORTION_RADTAN, "unsupported distortion model");
+  SVOH_REQUIRE(ctx, camera_is_known(*cam), "unsupported distortion model");
+  SVOH_REQUIRE(ctx, cam->distortion != SVOH_DISTORTION_ATAN || (cam->d[0] != 0.0 && std::isfinite(cam->d[0])),
+               "ATAN (fisheye) camera: s = d[0] must be finite and non-zero");
   SVOH_REQUIRE(ctx, ctx->cand_pending_n == 0, "a candidate projection is queued already: collect first");
   if (align_result_index >= 0) {
     SVOH_REQUIRE(ctx, T_b != nullptr, "T_post is NULL");
@@ -3409,7 +3422,9 @@ static int enqueue_candidates(svoh_ctx* ctx, const svoh_camera* cam, const svoh_
   a.v = reinterpret_cast<const double*>(d + o_v); a.mu = reinterpret_cast<const double*>(d + o_mu);
   a.px = reinterpret_cast<double*>(d + o_px); a.visible = d + o_vis;
   a.n = n; a.n_kf = n_kf;
-  hipLaunchKernelGGL(project_candidates_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
+  // by the camera's family: no Jacobian is evaluated here, so ATAN runs like EQUIDISTANT
+  if (camera_is_narrow(*cam)) hipLaunchKernelGGL(project_candidates_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(project_candidates_wide_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(ctx, SVOH_ERR_HIP, "project_candidates launch failed: %s", hipGetErrorString(e));
   SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, h + o_px, d + o_px, total - o_px));
@@ -3610,7 +3625,8 @@ struct MultiCandidateArgs {
 };
 
 // per point exactly the arithmetic of project_candidates_kernel
-__global__ __launch_bounds__(256) void project_candidates_multi_kernel(const MultiCandidateArgs a)
+template <class Cam>
+__device__ __forceinline__ void project_candidates_multi_body(const MultiCandidateArgs& a)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= a.n) return;
@@ -3619,7 +3635,7 @@ __global__ __launch_bounds__(256) void project_candidates_multi_kernel(const Mul
   const svoh_candidate_job& jb = a.jobs[j];
   Rigid T_f_w = load_rigid(jb.T_f_w_or_T_cam_imu);
   if (jb.align_result_index >= 0) T_f_w = mul(mul(T_f_w, load_rigid(a.align_results[a.result_dev_index[j]].T_icur_iref)), load_rigid(jb.T_imu_world_ref));
-  const CamModel cm = load_camera(jb.cam);
+  const Cam cm = load_camera_as<Cam>(jb.cam);
   Vec3 xyz = { a.v[3 * i], a.v[3 * i + 1], a.v[3 * i + 2] };
   bool ok = true;
   if (a.kind[i]) {
@@ -3650,6 +3666,10 @@ __global__ __launch_bounds__(256) void project_candidates_multi_kernel(const Mul
   a.px[2 * i] = u; a.px[2 * i + 1] = v;
   a.visible[i] = ok ? 1 : 0;
 }
+
+// the narrow family (NONE | RADTAN) under the name it always had, and the twin for launches with an EQUIDISTANT or ATAN camera
+__global__ __launch_bounds__(256) void project_candidates_multi_kernel(const MultiCandidateArgs a) { project_candidates_multi_body<CamModel>(a); }
+__global__ __launch_bounds__(256) void project_candidates_multi_wide_kernel(const MultiCandidateArgs a) { project_candidates_multi_body<CamModelWide>(a); }
 
 // ---- svoh_select_matches_batch: the loop of matchCandidates (reprojector.cpp:342-382) over given matches, one workgroup per list --
 // Sequentially: candidate k is tried iff its cell is free when the loop gets there; a success takes the cell; the loop ends with the
@@ -3749,7 +3769,8 @@ struct RangeCandidateArgs {
   int n, n_jobs, n_ranges;
 };
 
-__global__ __launch_bounds__(256) void project_candidates_ranges_kernel(const RangeCandidateArgs a)
+template <class Cam>
+__device__ __forceinline__ void project_candidates_ranges_body(const RangeCandidateArgs& a)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= a.n) return;
@@ -3764,7 +3785,7 @@ __global__ __launch_bounds__(256) void project_candidates_ranges_kernel(const Ra
   const svoh_candidate_job& jb = a.jobs[j];
   Rigid T_f_w = load_rigid(jb.T_f_w_or_T_cam_imu);
   if (jb.align_result_index >= 0) T_f_w = mul(mul(T_f_w, load_rigid(a.align_results[a.result_dev_index[j]].T_icur_iref)), load_rigid(jb.T_imu_world_ref));
-  const CamModel cm = load_camera(jb.cam);
+  const Cam cm = load_camera_as<Cam>(jb.cam);
   Vec3 xyz = { 0.0, 0.0, 0.0 };
   bool ok = true;
   if (a.kind[i]) {
@@ -3799,6 +3820,10 @@ __global__ __launch_bounds__(256) void project_candidates_ranges_kernel(const Ra
   a.px[2 * i] = u; a.px[2 * i + 1] = v;
   a.visible[i] = ok ? 1 : 0;
 }
+
+// the narrow family (NONE | RADTAN) under the name it always had, and the twin for launches with an EQUIDISTANT or ATAN camera
+__global__ __launch_bounds__(256) void project_candidates_ranges_kernel(const RangeCandidateArgs a) { project_candidates_ranges_body<CamModel>(a); }
+__global__ __launch_bounds__(256) void project_candidates_ranges_wide_kernel(const RangeCandidateArgs a) { project_candidates_ranges_body<CamModelWide>(a); }
 
 }  // namespace svoh
 
@@ -3954,10 +3979,13 @@ static int enqueue_staged_candidates(svoh_ctx* ctx, bool with_units)
   uint8_t* d = static_cast<uint8_t*>(ctx->d_cand_multi.ptr);
   svoh_candidate_job* jobs = reinterpret_cast<svoh_candidate_job*>(h + st.o_jobs);
   uint32_t* dev_idx = reinterpret_cast<uint32_t*>(jobs + st.n_jobs);
-  bool any_result = false;
+  bool any_result = false, any_wide = false;   // one wide camera among the jobs: the whole launch runs the wide twin
   for (int j = 0; j < st.n_jobs; ++j) {
     const svoh_candidate_job& jb = jobs[j];
-    SVOH_REQUIRE(ctx, jb.cam.distortion == SVOH_DISTORTION_NONE || jb.cam.distortion == SVOH_DISTORTION_RADTAN, "unsupported distortion model");
+    SVOH_REQUIRE(ctx, camera_is_known(jb.cam), "unsupported distortion model");
+    SVOH_REQUIRE(ctx, jb.cam.distortion != SVOH_DISTORTION_ATAN || (jb.cam.d[0] != 0.0 && std::isfinite(jb.cam.d[0])),
+                 "ATAN (fisheye) camera: s = d[0] must be finite and non-zero");
+    any_wide = any_wide || !camera_is_narrow(jb.cam);
     SVOH_REQUIRE(ctx, jb.n_kf >= 0 && jb.kf_begin >= 0 && (int64_t)jb.kf_begin + jb.n_kf <= st.n_kf, "a job's keyframe range leaves the table");
     SVOH_REQUIRE(ctx, jb.n_points >= 0 && jb.point_begin >= 0 && (int64_t)jb.point_begin + jb.n_points <= st.n_points, "a job's point range leaves the arrays");
     dev_idx[j] = 0;
@@ -3995,7 +4023,8 @@ static int enqueue_staged_candidates(svoh_ctx* ctx, bool with_units)
     a.v = any_landmark ? reinterpret_cast<const double*>(d + st.o_v) : nullptr;
     a.px = reinterpret_cast<double*>(d + st.o_px); a.visible = d + st.o_vis;
     a.n = st.n_points; a.n_jobs = st.n_jobs; a.n_ranges = st.n_kf;
-    hipLaunchKernelGGL(project_candidates_ranges_kernel, dim3((unsigned)((st.n_points + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    if (any_wide) hipLaunchKernelGGL(project_candidates_ranges_wide_kernel, dim3((unsigned)((st.n_points + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(project_candidates_ranges_kernel, dim3((unsigned)((st.n_points + 255) / 256)), dim3(256), 0, ctx->stream, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(ctx, SVOH_ERR_HIP, "project_candidates_ranges launch failed: %s", hipGetErrorString(e));
     SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, h + st.o_px, d + st.o_px, st.o_ranges - st.o_px));
@@ -4013,7 +4042,8 @@ static int enqueue_staged_candidates(svoh_ctx* ctx, bool with_units)
   a.v = reinterpret_cast<const double*>(d + st.o_v); a.mu = reinterpret_cast<const double*>(d + st.o_mu);
   a.px = reinterpret_cast<double*>(d + st.o_px); a.visible = d + st.o_vis;
   a.n = st.n_points; a.n_jobs = st.n_jobs;
-  hipLaunchKernelGGL(project_candidates_multi_kernel, dim3((unsigned)((st.n_points + 255) / 256)), dim3(256), 0, ctx->stream, a);
+  if (any_wide) hipLaunchKernelGGL(project_candidates_multi_wide_kernel, dim3((unsigned)((st.n_points + 255) / 256)), dim3(256), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(project_candidates_multi_kernel, dim3((unsigned)((st.n_points + 255) / 256)), dim3(256), 0, ctx->stream, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(ctx, SVOH_ERR_HIP, "project_candidates_multi launch failed: %s", hipGetErrorString(e));
   SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, h + st.o_px, d + st.o_px, st.total - st.o_px));

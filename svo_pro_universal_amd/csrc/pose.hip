@@ -14,6 +14,7 @@
 // nth_element; sums differ from the sequential reference in rounding only.
 #include <cstdlib>
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <thread>
 #include <type_traits>
@@ -64,7 +65,7 @@ __device__ __forceinline__ float tukey_weight_f(float e)
   return 0.0f;
 }
 
-__device__ __forceinline__ bool is_edgelet_type(int t) { return t == SVOH_FT_EDGELET || t == SVOH_FT_EDGELET_SEED || t == SVOH_FT_EDGELET_SEED_CONVERGED; }
+__host__ __device__ __forceinline__ bool is_edgelet_type(int t) { return t == SVOH_FT_EDGELET || t == SVOH_FT_EDGELET_SEED || t == SVOH_FT_EDGELET_SEED_CONVERGED; }
 
 // J (rows x 6) = A (rows x 3) * R_cam_imu * [I | -skew(p_in_imu)]   (frame.h:342-397)
 template <int ROWS>
@@ -85,9 +86,10 @@ __device__ __forceinline__ void chain_G(const double* A, const double* R, const 
 
 // one measurement (pose_optimizer.cpp:338-627); acc = upper triangle of H (21) + g (6), row-major packing
 // ET (the error type) and WANT_J are compile-time: each kernel instance carries one error model only, which is what
-// keeps it within 256 registers (two waves per SIMD)
-template <int ET, bool WANT_J>
-__device__ __forceinline__ void pose_residual(const CamModel& cm, const Rigid& T_cam_imu, const double* Rci,
+// keeps it within 256 registers (two waves per SIMD).  Cam is the camera family of the kernel (CamModel | CamModelWide):
+// project3 / project3_jacobian are its overloads, and the unit-plane error evaluates neither
+template <int ET, bool WANT_J, class Cam>
+__device__ __forceinline__ void pose_residual(const Cam& cm, const Rigid& T_cam_imu, const double* Rci,
                               const Rigid& T_imu_world, const double* f, const double* px, const double* grad,
                               const Vec3& xyz_world, bool edgelet, double measurement_sigma, double& unwhitened_error,
                               double* acc /* may be NULL */)
@@ -228,8 +230,10 @@ __device__ T rank_select(const T* vals, int n, int k, int tid, T* s_out)
 // negative scale or an undefined shift)
 __device__ __forceinline__ int pose_level(int l) { return l < 0 ? 0 : (l > 29 ? 29 : l); }
 
-template <int NT, int ET>
-__global__ __launch_bounds__(NT) void pose_optimize_kernel(const PoseArgs a)
+// The kernel's body, over the camera family as well: pose_optimize_kernel<NT, ET> below is it for CamModel (NONE |
+// RADTAN), pose_optimize_wide_kernel<NT, ET> for CamModelWide (those and EQUIDISTANT | ATAN).
+template <int NT, int ET, class Cam>
+__device__ __forceinline__ void pose_optimize_body(const PoseArgs& a)
 {
   constexpr int NACC = 27, NW = NT / 64;
   // start errors as float values, later final errors (double); sized by the launch to the largest bundle of the
@@ -264,13 +268,13 @@ __global__ __launch_bounds__(NT) void pose_optimize_kernel(const PoseArgs a)
   for (int c = 0; c < pb.n_cams; ++c) n_total += cams[c].n_features;
   auto for_each_feature = [&](auto&& fn) {
     int c = -1, lo = 0, hi = 0;   // camera of the current feature and its index range [lo, hi)
-    CamModel cm = {};
+    Cam cm = {};
     Rigid T_cam_imu = {};
     double Rci[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
     for (int j = tid; j < n_total; j += NT) {
       if (j >= hi) {
         do { ++c; lo = hi; hi += cams[c].n_features; } while (j >= hi);
-        cm = load_camera(cams[c].cam);
+        cm = load_camera_as<Cam>(cams[c].cam);
         T_cam_imu = load_rigid(cams[c].T_cam_imu);
         to_matrix(T_cam_imu.q, Rci);
       }
@@ -283,7 +287,7 @@ __global__ __launch_bounds__(NT) void pose_optimize_kernel(const PoseArgs a)
   // ---- start errors and the MAD scale (pose_optimizer.cpp:48-52) ----
   {
     const Rigid T = s_T;
-    for_each_feature([&](const CamModel& cm, const Rigid& T_cam_imu, const double* Rci, long long gi) {
+    for_each_feature([&](const Cam& cm, const Rigid& T_cam_imu, const double* Rci, long long gi) {
       const int scale = 1 << pose_level(a.level[gi]);
       double ue;
       const Vec3 X = { a.xyz[3 * gi], a.xyz[3 * gi + 1], a.xyz[3 * gi + 2] };
@@ -321,7 +325,7 @@ __global__ __launch_bounds__(NT) void pose_optimize_kernel(const PoseArgs a)
 #pragma unroll
     for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
     const Rigid T = s_T;
-    for_each_feature([&](const CamModel& cm, const Rigid& T_cam_imu, const double* Rci, long long gi) {
+    for_each_feature([&](const Cam& cm, const Rigid& T_cam_imu, const double* Rci, long long gi) {
       const int scale = 1 << pose_level(a.level[gi]);
       const bool edgelet = is_edgelet_type(a.type[gi]);
       double sigma = measurement_sigma * scale;
@@ -427,7 +431,7 @@ __global__ __launch_bounds__(NT) void pose_optimize_kernel(const PoseArgs a)
         const long long gi = pb.arr_off + cams[c].feat_off + i;
         if (!a.usable[gi]) { a.outlier[gi] = 0; a.final_error[gi] = 0.0; }
       }
-    for_each_feature([&](const CamModel& cm, const Rigid& T_cam_imu, const double* Rci, long long gi) {
+    for_each_feature([&](const Cam& cm, const Rigid& T_cam_imu, const double* Rci, long long gi) {
       const bool edgelet = is_edgelet_type(a.type[gi]);
       double ue;
       const Vec3 X = { a.xyz[3 * gi], a.xyz[3 * gi + 1], a.xyz[3 * gi + 2] };
@@ -457,6 +461,20 @@ __global__ __launch_bounds__(NT) void pose_optimize_kernel(const PoseArgs a)
     res.reserved = 0;
   }
 }
+
+template <int NT, int ET>
+__global__ __launch_bounds__(NT) void pose_optimize_kernel(const PoseArgs a) { pose_optimize_body<NT, ET, CamModel>(a); }
+
+// The twin for a launch in which some camera is EQUIDISTANT or ATAN and the error type evaluates the camera (the
+// image plane, and the bearing difference's edgelets): the same body with the wide camera maths compiled in.  Under a
+// name of its own: the register budget of pose_optimize_kernel<...> is not this kernel's.
+template <int NT, int ET>
+__global__ __launch_bounds__(NT) void pose_optimize_wide_kernel(const PoseArgs a) { pose_optimize_body<NT, ET, CamModelWide>(a); }
+
+// is pose_optimize_wide_kernel<512, IMAGE_PLANE> instantiated?  Only while the built object shows it within 256
+// registers without a spill (512 threads are two waves per SIMD); a wide launch of 512 threads runs 256 otherwise.
+// Built: 256 registers WITH 49 spilled (the <256> build takes 306) -- not instantiated.
+constexpr bool kPoseWide512 = false;
 
 
 // ---- Point::optimize (second half) ---------------------------------------------------------
@@ -574,6 +592,13 @@ static int run_pose_batch(svoh_ctx* ctx, const svoh_pose_options* options, int n
   SVOH_REQUIRE(ctx, options->max_iter >= 1 && options->error_type >= 0 && options->error_type <= 2, "bad max_iter / error_type");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
 
+  // The wide twin runs a launch whose error type evaluates the camera (UNIT_PLANE uses f and the point only) and in
+  // which at least one camera is EQUIDISTANT or ATAN; every other launch runs the narrow kernel.  ATAN has no Jacobian
+  // (AtanDistortion::jacobian is fatal in the reference): it is refused wherever one would be evaluated, before
+  // anything is staged -- with IMAGE_PLANE, and with BEARING_DIFF if a usable feature is an edgelet (the packed
+  // entry's types live on the device and cannot be checked: refused).
+  const bool cam_evaluated = options->error_type != SVOH_POSE_ERR_UNIT_PLANE;
+  bool any_wide = false;
   size_t n_cams_total = 0, n_feat_total = 0, max_meas = 0;
   for (int p = 0; p < n_problems; ++p) {
     const svoh_pose_problem& pb = problems[p];
@@ -585,10 +610,23 @@ static int run_pose_batch(svoh_ctx* ctx, const svoh_pose_options* options, int n
       SVOH_REQUIRE(ctx, packed || cam.n_features == 0 ||
                             (cam.px && cam.f && cam.grad && cam.level && cam.type && cam.xyz_world && cam.usable),
                    "NULL feature array");
-      SVOH_REQUIRE(ctx, cam.cam.distortion == SVOH_DISTORTION_NONE || cam.cam.distortion == SVOH_DISTORTION_RADTAN,
-                   "unsupported distortion model");
+      SVOH_REQUIRE(ctx, camera_is_known(cam.cam), "unsupported distortion model");
+      SVOH_REQUIRE(ctx, cam.cam.distortion != SVOH_DISTORTION_ATAN || (cam.cam.d[0] != 0.0 && std::isfinite(cam.cam.d[0])),
+                   "ATAN (fisheye) camera: s = d[0] must be finite and non-zero");
+      any_wide = any_wide || !camera_is_narrow(cam.cam);
+      const bool no_jacobian = cam_evaluated && !camera_has_jacobian(cam.cam);
+      if (no_jacobian && options->error_type == SVOH_POSE_ERR_IMAGE_PLANE)
+        return set_error(ctx, SVOH_ERR_UNSUPPORTED, "the ATAN (fisheye) camera has no Jacobian (AtanDistortion::jacobian): the image-plane error needs one");
+      if (no_jacobian && packed)
+        return set_error(ctx, SVOH_ERR_UNSUPPORTED, "the ATAN (fisheye) camera has no Jacobian (AtanDistortion::jacobian): the bearing difference needs one "
+                                                    "for edgelets, and the packed entry's feature types cannot be checked on the host");
       if (!packed)   // device-resident levels are clamped to 0..29 by the kernel instead (pose_level)
-        for (int i = 0; i < cam.n_features; ++i) SVOH_REQUIRE(ctx, cam.level[i] >= 0 && cam.level[i] < 30, "feature level out of range");
+        for (int i = 0; i < cam.n_features; ++i) {
+          SVOH_REQUIRE(ctx, cam.level[i] >= 0 && cam.level[i] < 30, "feature level out of range");
+          if (no_jacobian && cam.usable[i] && is_edgelet_type(cam.type[i]))
+            return set_error(ctx, SVOH_ERR_UNSUPPORTED, "the ATAN (fisheye) camera has no Jacobian (AtanDistortion::jacobian): the bearing difference needs one "
+                                                        "for its edgelets");
+        }
       n += (size_t)cam.n_features;
     }
     SVOH_REQUIRE(ctx, n <= (size_t)kPoseMaxMeas, "more than 4096 features in one bundle");
@@ -690,8 +728,28 @@ static int run_pose_batch(svoh_ctx* ctx, const svoh_pose_options* options, int n
   // a few large bundles: one feature per lane (measured, scripts/perf_pose_scaling.py: 2 x 160 features 0.064 ms with 256 threads)
   if (n_problems * 2 <= ctx->num_cus && (int)max_meas > kPoseThreads && options->error_type != SVOH_POSE_ERR_BEARING_DIFF) nt = 512;
   { const int v = ctx->knobs.pose_threads; if (v == 64 || v == kPoseThreads || (v == 512 && options->error_type != SVOH_POSE_ERR_BEARING_DIFF)) nt = v; }
+  const bool wide = cam_evaluated && any_wide;
+  if (wide && nt == 512 && !kPoseWide512) nt = kPoseThreads;
   auto launch = [&](auto et) {
     constexpr int ET = decltype(et)::value;
+    if constexpr (ET != SVOH_POSE_ERR_UNIT_PLANE) {
+      if (wide) {
+        // every value of nt launches: whatever is neither 64 nor an instantiated 512 runs the 256-thread build
+        bool launched = false;
+        if (nt == 64) {
+          hipLaunchKernelGGL((pose_optimize_wide_kernel<64, ET>), dim3((unsigned)n_problems), dim3(64), err_bytes, ctx->stream, a);
+          launched = true;
+        }
+        if constexpr (ET == SVOH_POSE_ERR_IMAGE_PLANE && kPoseWide512) {
+          if (nt == 512) {
+            hipLaunchKernelGGL((pose_optimize_wide_kernel<512, ET>), dim3((unsigned)n_problems), dim3(512), err_bytes, ctx->stream, a);
+            launched = true;
+          }
+        }
+        if (!launched) hipLaunchKernelGGL((pose_optimize_wide_kernel<kPoseThreads, ET>), dim3((unsigned)n_problems), dim3(kPoseThreads), err_bytes, ctx->stream, a);
+        return;
+      }
+    }
     if (nt == 64) hipLaunchKernelGGL((pose_optimize_kernel<64, ET>), dim3((unsigned)n_problems), dim3(64), err_bytes, ctx->stream, a);
     else if (nt == 512) {
       if constexpr (ET != SVOH_POSE_ERR_BEARING_DIFF) hipLaunchKernelGGL((pose_optimize_kernel<512, ET>), dim3((unsigned)n_problems), dim3(512), err_bytes, ctx->stream, a);

@@ -111,6 +111,42 @@ class Context(object):
                                                None if J is None else J.ctypes.data, fb.ctypes.data))
         return px, J, fb
 
+    # ---- candidate projection (Reprojector::reprojectFrames, f-4) ----------
+    def project_candidates_enqueue(self, cam, T_f_w, T_world_kf, kind, kf, v, mu, align_result_index=-1, T_cam_imu=None,
+                                   T_imu_world_ref=None):
+        """svoh_project_candidates_enqueue.  With align_result_index >= 0 the current frame's pose is composed on the device as
+        T_cam_imu * T_icur_iref * T_imu_world_ref from that result of the alignment queued in front (T_f_w is then not
+        used); otherwise T_f_w is the pose.  kind n (0 world point, 1 seed of keyframe kf[i]), v 3n, mu n.  Any camera
+        model: no Jacobian is evaluated.  Returns n for project_candidates_collect."""
+        kind = np.ascontiguousarray(kind, np.uint8).ravel()
+        n = kind.size
+        kf = np.ascontiguousarray(kf, np.int32).ravel()
+        v = np.ascontiguousarray(v, np.float64).ravel()
+        mu = np.ascontiguousarray(mu, np.float64).ravel()
+        if kf.size != n or v.size != 3 * n or mu.size != n:
+            raise ValueError("kind, kf, v and mu do not describe the same number of points")
+        composed = align_result_index >= 0
+        if composed and (T_cam_imu is None or T_imu_world_ref is None):
+            raise ValueError("align_result_index needs T_cam_imu and T_imu_world_ref")
+        Ta = _se3(T_cam_imu if composed else T_f_w)
+        Tb = _se3(T_imu_world_ref) if composed else None
+        Tk = (capi.svoh_se3 * max(1, len(T_world_kf)))(*[_se3(t) for t in T_world_kf])
+        c = _camera(cam)
+        self._check(self.lib.svoh_project_candidates_enqueue(self.h, C.byref(c), C.byref(Ta), None if Tb is None else C.byref(Tb),
+                                                             int(align_result_index), len(T_world_kf), Tk, n, kind.ctypes.data,
+                                                             kf.ctypes.data, v.ctypes.data, mu.ctypes.data))
+        return n
+
+    def project_candidates_collect(self, n):
+        """svoh_project_candidates_collect: (px [n, 2], visible [n] bool) of the queued projection."""
+        px, vis = np.zeros(2 * n), np.zeros(n, np.uint8)
+        self._check(self.lib.svoh_project_candidates_collect(self.h, int(n), px.ctypes.data, vis.ctypes.data))
+        return px.reshape(n, 2), vis.astype(bool)
+
+    def project_candidates(self, cam, T_f_w, T_world_kf, kind, kf, v, mu):
+        """svoh_project_candidates: the points of the local map into the frame with pose T_f_w; (px [n, 2], visible [n])."""
+        return self.project_candidates_collect(self.project_candidates_enqueue(cam, T_f_w, T_world_kf, kind, kf, v, mu))
+
     # ---- frames -----------------------------------------------------------
     def upload_pyramid(self, levels):
         n = len(levels)
