@@ -378,6 +378,15 @@ int svoh_sparse_align_last_launch_info(svoh_ctx* ctx, int32_t* geometry_key, int
  * is no multiple of 16 keeps its last columns unwritten, on the device as in the reference: not a case of this query.) */
 int svoh_sparse_align_last_launch_lds(svoh_ctx* ctx, int32_t* lds_img_bytes);
 
+/* Which launch lane the most recent launch of the alignment kernel took (full run or evaluation).  A launch of the batch build (256 threads, at least one problem per compute unit;
+ * not a keyed, evaluation or split launch) that is queued right behind another one nobody has waited for runs on a second
+ * stream with a feature workspace of its own, beside the tail of the launch before it: lane 1; the launch behind that one is
+ * on lane 0 again, the context's stream.  Every other launch runs on lane 0.  *lanes: 2 once the context has made its second
+ * lane (its first launch of the batch build does, unless SVOH_ALIGN_OVERLAP=0), else 1.  *lane1_launches (may be NULL): how
+ * many launches of this context have taken lane 1.  Host-side bookkeeping, no synchronisation; fails before the first
+ * launch. */
+int svoh_sparse_align_last_launch_lane(svoh_ctx* ctx, int32_t* lane, int32_t* lanes, uint64_t* lane1_launches);
+
 /* Diagnostic/parity entry: evaluate H (8x8 col-major), g (8), chi2, n_meas for
  * ONE problem at a given level and state, i.e. SparseImgAlign::evaluateError
  * (sparse_img_align.cpp:115-156) on a fresh level.  visibility (may be NULL)

@@ -3,11 +3,14 @@
 
   rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d DIR -o NAME -- python bench.py
   scripts/align_gap_timeline.py DIR/**/NAME_kernel_trace.csv DIR/**/NAME_memory_copy_trace.csv [n_gaps_listed]
+  scripts/align_gap_timeline.py DIR/**/NAME_kernel_trace.csv - [n_gaps_listed]        (a pass with --kernel-trace alone)
 
 For every pair of consecutive alignment kernels less than 2 ms apart (the steps of one queue): the idle time between them, and every
 other kernel and every copy that runs in it or ends in it, with its duration and where it starts relative to the first kernel's end.
 Then the medians over the steady-state gaps, and where the copies of a step ran relative to the kernels (inside a gap or beside a
-kernel).  Times in microseconds."""
+kernel).  Last, every alignment kernel's begin and end, counted from the first one's begin, and how far its begin lies from the end
+of the kernel before it: negative where the launch lanes (csrc/svoh_internal.h) start a kernel in the tail of the one before.
+Times in microseconds."""
 import csv
 import statistics
 import sys
@@ -25,11 +28,34 @@ def col(r, *names):
     return ""
 
 
+def kernel_timeline(align, n_list):
+    """begin and end of the alignment kernels of the last queue (consecutive kernels less than 2 ms apart), and of the n_list before"""
+    queue = [align[-1]]
+    for k in reversed(align[:-1]):
+        if queue[0][0] - k[1] > 2e6:
+            break
+        queue.insert(0, k)
+    t0 = queue[0][0]
+    print("alignment kernels of the last queue (%d): begin, end (us from the first one's begin), duration, begin - end of the kernel before" % len(queue))
+    starts_inside = 0
+    for i, k in enumerate(queue):
+        d = (k[0] - queue[i - 1][1]) / 1e3 if i else 0.0
+        starts_inside += 1 if i and d < 0 else 0
+        if i < n_list or i >= len(queue) - n_list:
+            print("    #%-3d begin %10.1f  end %10.1f  duration %8.1f  %s" % (i, (k[0] - t0) / 1e3, (k[1] - t0) / 1e3, (k[1] - k[0]) / 1e3,
+                                                                              ("begin - previous end %+8.1f" % d) if i else ""))
+    if len(queue) > 1:
+        d_all = [(b[0] - a[1]) / 1e3 for a, b in zip(queue, queue[1:])]
+        print("    kernels that begin before the kernel before them has ended: %d of %d;  begin - previous end: median %+.1f us, min %+.1f, max %+.1f"
+              % (starts_inside, len(queue) - 1, statistics.median(d_all), min(d_all), max(d_all)))
+        print("    the queue: %.1f us from the first begin to the last end, %.1f us per kernel" % ((queue[-1][1] - t0) / 1e3, (queue[-1][1] - t0) / 1e3 / len(queue)))
+
+
 def main(kernel_csv, copy_csv, n_list=6):
     ks = [(int(col(r, "Start_Timestamp")), int(col(r, "End_Timestamp")), col(r, "Kernel_Name")) for r in rows(kernel_csv)]
     cs = [(int(col(r, "Start_Timestamp")), int(col(r, "End_Timestamp")),
            "copy %s%s" % (col(r, "Direction").replace("MEMORY_COPY_", ""), (" %s B" % col(r, "Bytes", "Size")) if col(r, "Bytes", "Size") else ""))
-          for r in rows(copy_csv)]
+          for r in (rows(copy_csv) if copy_csv != "-" else [])]
     align = sorted(k for k in ks if "sparse_align_kernel" in k[2])
     others = sorted([k for k in ks if "sparse_align_kernel" not in k[2]] + cs)
     print("%d alignment kernels, %d other kernels, %d copies" % (len(align), len(ks) - len(align), len(cs)))
@@ -43,6 +69,7 @@ def main(kernel_csv, copy_csv, n_list=6):
     if not gaps:
         print("no consecutive alignment kernels found")
         return
+    kernel_timeline(align, n_list)
     for idle, a, b, inside in gaps[-n_list:]:
         print("gap %8.1f us   (kernel before %.1f us, after %.1f us)" % (idle, (a[1] - a[0]) / 1e3, (b[1] - b[0]) / 1e3))
         t = a[1]

@@ -295,7 +295,7 @@ EXPORTS = [
     "svoh_upload_pyramid", "svoh_build_pyramid", "svoh_build_pyramid_batch",
     "svoh_download_level", "svoh_frame_info", "svoh_release_frame", "svoh_camera_maths", "svoh_context_stats", "svoh_reload_knobs", "svoh_set_kernel_timing", "svoh_set_copy_policy", "svoh_set_align_geometry_classes",
     "svoh_sparse_align_batch", "svoh_sparse_align_enqueue", "svoh_sparse_align_fetch", "svoh_sparse_align_fetch_all",
-    "svoh_sparse_align_evaluate", "svoh_sparse_align_last_kernel_ms", "svoh_sparse_align_kernel_ms_history", "svoh_sparse_align_last_launch_info", "svoh_sparse_align_last_launch_lds",
+    "svoh_sparse_align_evaluate", "svoh_sparse_align_last_kernel_ms", "svoh_sparse_align_kernel_ms_history", "svoh_sparse_align_last_launch_info", "svoh_sparse_align_last_launch_lds", "svoh_sparse_align_last_launch_lane",
     "svoh_sparse_align_split_buffers", "svoh_sparse_align_split_init", "svoh_sparse_align_partial_sums", "svoh_sparse_align_gn_update",
     "svoh_klt_track_batch", "svoh_klt_track_multi", "svoh_klt_track_indexed", "svoh_last_kernel_ms", "svoh_last_kernel_counters",
     "svoh_match_direct_batch", "svoh_match_direct_batch_pixelwise", "svoh_matcher_begin_deferred", "svoh_matcher_collect", "svoh_matcher_flush", "svoh_matcher_deferred_set_cur_frame", "svoh_optimize_pose_batch_hook",
@@ -402,6 +402,7 @@ def load(path=None):
     lib.svoh_sparse_align_last_kernel_ms.argtypes = [C.c_void_p, P(C.c_float)]
     lib.svoh_sparse_align_kernel_ms_history.argtypes = [C.c_void_p, C.c_int, P(C.c_float), P(C.c_int)]
     lib.svoh_sparse_align_last_launch_info.argtypes = [C.c_void_p, P(C.c_int32), P(C.c_int32), P(C.c_int32)]
+    lib.svoh_sparse_align_last_launch_lane.argtypes = [C.c_void_p, P(C.c_int32), P(C.c_int32), P(C.c_uint64)]
     lib.svoh_sparse_align_last_launch_lds.argtypes = [C.c_void_p, P(C.c_int32)]
     lib.svoh_sparse_align_split_buffers.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_void_p)]
     lib.svoh_sparse_align_split_init.argtypes = [C.c_void_p, P(svoh_align_problem), C.c_void_p]

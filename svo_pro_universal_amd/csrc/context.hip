@@ -64,29 +64,31 @@ static unsigned copy_blocks(size_t n16)
   return (unsigned)(blocks > cap ? cap : (blocks ? blocks : 1));
 }
 
-hipError_t svoh_copy_to_host(svoh_ctx* ctx, void* dst_pinned, const void* src_device, size_t bytes)
+hipError_t svoh_copy_to_host(svoh_ctx* ctx, void* dst_pinned, const void* src_device, size_t bytes, hipStream_t on)
 {
   if (bytes == 0) return hipSuccess;
+  const hipStream_t st = on ? on : ctx->stream;
   const bool by_kernel = copy_by_kernel(ctx, dst_pinned, src_device, bytes, (size_t)16 << 10);
-  if (!by_kernel) return hipMemcpyAsync(dst_pinned, src_device, bytes, hipMemcpyDeviceToHost, ctx->stream);
+  if (!by_kernel) return hipMemcpyAsync(dst_pinned, src_device, bytes, hipMemcpyDeviceToHost, st);
   const size_t n16 = bytes / 16;
   const int n_tail = (int)(bytes - n16 * 16);
   const unsigned blocks = copy_blocks(n16);
-  hipLaunchKernelGGL(svoh_copy_to_host_kernel, dim3(blocks), dim3(256), 0, ctx->stream, static_cast<uint4*>(dst_pinned),
+  hipLaunchKernelGGL(svoh_copy_to_host_kernel, dim3(blocks), dim3(256), 0, st, static_cast<uint4*>(dst_pinned),
                      static_cast<const uint4*>(src_device), n16, static_cast<uint8_t*>(dst_pinned) + n16 * 16,
                      static_cast<const uint8_t*>(src_device) + n16 * 16, n_tail);
   return hipGetLastError();
 }
 
-hipError_t svoh_copy_to_device(svoh_ctx* ctx, void* dst_device, const void* src_pinned, size_t bytes)
+hipError_t svoh_copy_to_device(svoh_ctx* ctx, void* dst_device, const void* src_pinned, size_t bytes, hipStream_t on)
 {
   if (bytes == 0) return hipSuccess;
+  const hipStream_t st = on ? on : ctx->stream;
   const bool by_kernel = copy_by_kernel(ctx, dst_device, src_pinned, bytes, (size_t)32 << 10);
-  if (!by_kernel) return hipMemcpyAsync(dst_device, src_pinned, bytes, hipMemcpyHostToDevice, ctx->stream);
+  if (!by_kernel) return hipMemcpyAsync(dst_device, src_pinned, bytes, hipMemcpyHostToDevice, st);
   const size_t n16 = bytes / 16;
   const int n_tail = (int)(bytes - n16 * 16);
   const unsigned blocks = copy_blocks(n16);
-  hipLaunchKernelGGL(svoh_copy_to_host_kernel, dim3(blocks), dim3(256), 0, ctx->stream, static_cast<uint4*>(dst_device),
+  hipLaunchKernelGGL(svoh_copy_to_host_kernel, dim3(blocks), dim3(256), 0, st, static_cast<uint4*>(dst_device),
                      static_cast<const uint4*>(src_pinned), n16, static_cast<uint8_t*>(dst_device) + n16 * 16,
                      static_cast<const uint8_t*>(src_pinned) + n16 * 16, n_tail);
   return hipGetLastError();
@@ -456,6 +458,7 @@ void load_knobs_from_env(SvohKnobs& k)
   k.kernel_timing = get("SVOH_KERNEL_TIMING");
   k.copy_kernel = get("SVOH_COPY_KERNEL");
   k.align_side_copies = get("SVOH_ALIGN_SIDE_COPIES");
+  k.align_overlap = get("SVOH_ALIGN_OVERLAP");
 }
 
 static int build_pyramid_levels(svoh_ctx* ctx, hipStream_t stream, const std::shared_ptr<Slab>& slab, uint8_t* base, size_t fbytes, const size_t* offs, const int* ws,
@@ -484,6 +487,15 @@ int svoh_reload_knobs(svoh_ctx* ctx)
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   const int timing = ctx->knobs.kernel_timing, copy_policy = ctx->knobs.copy_kernel;
+  // the alignment plans its launches from these: both of its lanes run empty first (svoh_internal.h, launch lanes)
+  if (ctx->align_lane_stream) {
+    SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    SVOH_ALIGN_JOIN(ctx);
+    SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->align_lane_stream));
+    ctx->align_lane1_pending = false;
+    ctx->align_chain = false;
+  }
   load_knobs_from_env(ctx->knobs);
   if (ctx->knobs.kernel_timing == kKnobUnset) ctx->knobs.kernel_timing = timing;   // set by svoh_set_kernel_timing, not by the environment
   if (ctx->knobs.copy_kernel == kKnobUnset) ctx->knobs.copy_kernel = copy_policy;  // ... by svoh_set_copy_policy
@@ -536,8 +548,11 @@ try {
   if (ctx->upload_stream) { (void)hipStreamSynchronize(ctx->upload_stream); }
   // the alignment's copy stream: results of launches nobody fetched may still be on their way to h_results (a copy that was
   // held back, svoh_internal.h, is dropped)
+  // (both lanes first: a copy queued on the copy stream waits for an event behind a kernel on one of them)
+  if (ctx->align_lane_stream) { (void)hipStreamSynchronize(ctx->align_lane_stream); }
   if (ctx->align_copy_stream) { (void)hipStreamSynchronize(ctx->align_copy_stream); (void)hipStreamDestroy(ctx->align_copy_stream); }
-  for (hipEvent_t ev : { ctx->ev_align_kernel[0], ctx->ev_align_kernel[1], ctx->ev_align_uploaded, ctx->ev_align_delivered })
+  if (ctx->align_lane_stream) { (void)hipStreamDestroy(ctx->align_lane_stream); }
+  for (hipEvent_t ev : { ctx->ev_align_kernel[0], ctx->ev_align_kernel[1], ctx->ev_align_uploaded, ctx->ev_align_delivered, ctx->ev_align_front, ctx->ev_align_lane1 })
     if (ev) (void)hipEventDestroy(ev);
   ctx->frames.clear();
   for (auto& kv : ctx->masks) (void)hipFree(kv.second.ptr);
@@ -570,15 +585,28 @@ int svoh_synchronize(svoh_ctx* ctx)
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  // both lanes of the alignment: a launch on the second one is not on the context's stream
+  if (ctx->align_lane_stream) {
+    SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->align_lane_stream));
+    ctx->align_lane1_pending = false;
+  }
+  ctx->align_chain = false;
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
 
-void* svoh_stream(svoh_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
+// (whoever takes the stream puts work of their own on it: it waits for the alignment's second lane first, svoh_internal.h)
+void* svoh_stream(svoh_ctx* ctx)
+{
+  if (!ctx) return nullptr;
+  (void)svoh::align_join_lanes(ctx);
+  return (void*)ctx->stream;
+}
 
 int svoh_last_kernel_counters(svoh_ctx* ctx, uint64_t out[8])
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, out != nullptr && ctx->misc_launched && ctx->d_counters.ptr, "no counters yet");
+  SVOH_ALIGN_JOIN(ctx);
   if (ctx->unit_counts_pending) {
     const int rc = reduce_unit_counts_now(ctx, ctx->unit_counts_pending);
     if (rc != SVOH_OK) return rc;
@@ -611,6 +639,7 @@ try {
                             "level sizes must halve (createImgPyramid, frame.cpp:381-384)");
   }
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   size_t offs[SVOH_MAX_LEVELS]; int ws[SVOH_MAX_LEVELS], hs[SVOH_MAX_LEVELS];
   const size_t bytes = frame_layout(width[0], height[0], n_levels, offs, ws, hs);
   std::shared_ptr<Slab> slab;
@@ -635,6 +664,7 @@ try {
   SVOH_REQUIRE(ctx, rounding >= 0 && rounding <= 2, "bad rounding mode");
   SVOH_REQUIRE(ctx, (width >> (n_levels - 1)) > 0 && (height >> (n_levels - 1)) > 0, "too many levels");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   size_t offs[SVOH_MAX_LEVELS]; int ws[SVOH_MAX_LEVELS], hs[SVOH_MAX_LEVELS];
   const size_t fbytes = frame_layout(width, height, n_levels, offs, ws, hs);
   std::shared_ptr<Slab> slab;
@@ -700,6 +730,7 @@ static int build_pyramid_multi_on(svoh_ctx* ctx, hipStream_t stream, const uint8
   SVOH_REQUIRE(ctx, mem_space != SVOH_MEM_HOST_PINNED || n_images <= 256, "at most 256 page-locked images per call");
   for (int i = 0; i < n_images; ++i) SVOH_REQUIRE(ctx, imgs[i] != nullptr, "NULL image");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   size_t offs[SVOH_MAX_LEVELS]; int ws[SVOH_MAX_LEVELS], hs[SVOH_MAX_LEVELS];
   const size_t fbytes = frame_layout(width, height, n_levels, offs, ws, hs);
   std::shared_ptr<Slab> slab;
@@ -733,6 +764,7 @@ int svoh_build_pyramid_multi_prefetch(svoh_ctx* ctx, const uint8_t* const* imgs,
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   if (!ctx->upload_stream) {
     SVOH_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->upload_stream, hipStreamNonBlocking));
     SVOH_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_upload, hipEventDisableTiming));
@@ -753,6 +785,7 @@ try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   if (!ctx->upload_pending) return SVOH_OK;
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   SVOH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upload, 0));
   ctx->upload_pending = false;
   return SVOH_OK;
@@ -764,6 +797,7 @@ try {
   SVOH_REQUIRE(ctx, out && bytes > 0, "bad arguments");
   *out = nullptr;
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   SVOH_HIP_TRY(ctx, hipHostMalloc(out, bytes, hipHostMallocDefault));
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
@@ -773,6 +807,7 @@ try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   if (!p) return SVOH_OK;
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   SVOH_HIP_TRY(ctx, hipHostFree(p));   // (waits for work that may still read the block)
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
@@ -795,6 +830,7 @@ try {
   }
   if (total == 0) total = 64;
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   // the staging block may still be the source of the last upload's copy
   if (ctx->ev_features) SVOH_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_features));
   else SVOH_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_features, hipEventDisableTiming));
@@ -860,6 +896,7 @@ try {
   if (it == ctx->feature_sets.end()) return set_error(ctx, SVOH_ERR_BAD_HANDLE, "unknown feature-set handle %llu", (unsigned long long)features);
   // (no wait: batches queued before this call may still read the block; whoever gets it from the pool writes it on the
   // context's stream, behind them -- or hipFree waits for the device by itself)
+  SVOH_ALIGN_JOIN(ctx);
   ctx->feature_sets.erase(it);
   ++ctx->handle_generation;
   return SVOH_OK;
@@ -893,6 +930,7 @@ try {
   if (out_height) *out_height = f->lv[level].h;
   if (out) {
     SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    SVOH_ALIGN_JOIN(ctx);
     SVOH_HIP_TRY(ctx, hipMemcpyAsync(out, f->lv[level].data, (size_t)f->lv[level].w * f->lv[level].h,
                                      hipMemcpyDeviceToHost, ctx->stream));
     SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -940,6 +978,7 @@ try {
   if (J && !camera_has_jacobian(*cam))
     return set_error(ctx, SVOH_ERR_UNSUPPORTED, "the ATAN (fisheye) camera has no Jacobian (AtanDistortion::jacobian): pass J = NULL");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   // [xyz 3n | px 2n | J 6n | f 3n] doubles on the device
   const size_t nd = (size_t)n;
   SVOH_HIP_TRY(ctx, ctx->d_scratch2.reserve(14 * nd * sizeof(double)));
@@ -969,6 +1008,8 @@ try {
   // No wait here: kernels queued before this call may still read the frame.  Its slab either goes to the context's
   // pool -- the next frame is then written on the context's stream, behind those kernels -- or is freed by hipFree,
   // which waits for the device by itself.
+  // (behind those on the alignment's second lane too: svoh_internal.h, launch lanes)
+  SVOH_ALIGN_JOIN(ctx);
   ctx->frames.erase(it);
   ++ctx->handle_generation;
   return SVOH_OK;
@@ -982,6 +1023,7 @@ try {
   *out_mask = 0;
   SVOH_REQUIRE(ctx, width >= 1 && height >= 1 && width < (1 << 14) && height < (1 << 14) && pitch >= width, "bad mask size or pitch");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   svoh::Mask m;
   m.w = width; m.h = height;
   SVOH_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&m.ptr), (size_t)width * height));
@@ -1005,6 +1047,7 @@ try {
   if (it == ctx->masks.end())
     return set_error(ctx, SVOH_ERR_BAD_HANDLE, "unknown mask handle %llu", (unsigned long long)mask);
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   // a detector batch queued and not yet collected may still read the mask: the context's stream drains first
   SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   (void)hipFree(it->second.ptr);

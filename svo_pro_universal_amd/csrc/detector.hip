@@ -334,6 +334,7 @@ try {
   SVOH_REQUIRE(ctx, w < (1 << 14) && h < (1 << 14), "image larger than 16383 pixels a side");
   SVOH_REQUIRE(ctx, !mask || mask_pitch >= w, "mask pitch smaller than the image width");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   const int n_cols = (int)std::ceil((double)w / opt.cell_size), n_rows = (int)std::ceil((double)h / opt.cell_size);
   const int n_cells = n_cols * n_rows;
   if (max_n_features <= 0) return SVOH_OK;
@@ -528,6 +529,7 @@ static int enqueue_detect_cells(svoh_ctx* ctx, int n_frames, const svoh_frame_t*
     }
   const bool masked = !mask_ptr.empty();
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   const int n_cols = (int)std::ceil((double)w / opt.cell_size), n_rows = (int)std::ceil((double)h / opt.cell_size);
   const int n_cells = n_cols * n_rows;
   const size_t nf = (size_t)n_frames;
@@ -613,6 +615,7 @@ static int collect_detect_cells(svoh_ctx* ctx, uint64_t* corner_keys, uint64_t* 
   SVOH_REQUIRE(ctx, dp.in_flight, "no detector batch in flight");
   SVOH_REQUIRE(ctx, corner_keys && (!dp.edgelets || (edge_keys && edge_angles)), "NULL output array (edgelets were asked for: all three)");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   SVOH_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_detect));
   dp.in_flight = false;
   const uint8_t* hs = static_cast<const uint8_t*>(ctx->h_detect.ptr);
@@ -718,6 +721,7 @@ try {
   if (n == 0) return SVOH_OK;
   SVOH_REQUIRE(ctx, frames && frame_idx && level && px && bins && n_frames >= 1, "NULL argument");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
   const size_t o_lv = 0, o_jobs = al(sizeof(DevImage) * SVOH_MAX_LEVELS * (size_t)n_frames), o_bins = o_jobs + al(sizeof(AngleJob) * (size_t)n), total = o_bins + al(4 * (size_t)n);
   SVOH_HIP_TRY(ctx, ctx->h_scratch1.reserve(total));

@@ -452,6 +452,7 @@ try {
     if (rc != SVOH_OK) return rc;
   }
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
 
   // table of the distinct frames + two indices per track
   std::unordered_map<svoh_frame_t, int32_t> table;
@@ -511,6 +512,7 @@ try {
     if (rc != SVOH_OK) return rc;
   }
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   // every frame of the table must be usable as reference and as current frame of any
   // track: enough levels, and one common size per level (alignPyr2D assumes it)
   std::vector<const Frame*> tab((size_t)n_frames);

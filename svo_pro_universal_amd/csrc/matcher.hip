@@ -2931,6 +2931,7 @@ static int run_matcher(svoh_ctx* ctx, bool seeds, const svoh_matcher_options* mo
         SVOH_REQUIRE(ctx, fb->cur_frame_idx[i] >= 0 && fb->cur_frame_idx[i] < n_cur, "cur_frame_idx out of range");
   }
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
 
   std::vector<DevFrameView> views((size_t)n_ref_frames + n_cur);
   for (int k = 0; k < n_ref_frames; ++k) {
@@ -3178,6 +3179,7 @@ static int run_epipolar(svoh_ctx* ctx, const svoh_matcher_options* mopt, int n_r
     }
   }
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   std::vector<DevFrameView> views((size_t)n_ref_frames + n_cur);
   int ref_levels = 0;
   for (int k = 0; k < n_ref_frames; ++k) {
@@ -3400,6 +3402,7 @@ static int enqueue_candidates(svoh_ctx* ctx, const svoh_camera* cam, const svoh_
                  "no queued alignment result with this index");
   }
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   const size_t nd = (size_t)n;
   auto al = [](size_t b) { return (b + 63) & ~(size_t)63; };
   const size_t o_kf = 0, o_kind = o_kf + al(sizeof(svoh_se3) * (size_t)(n_kf > 0 ? n_kf : 1)), o_idx = o_kind + al(nd);
@@ -3514,6 +3517,7 @@ static int run_matcher_staged(svoh_ctx* ctx, bool seeds, const svoh_matcher_opti
                           (!A_cur_ref || A_cur_ref == at(st.o_A)), "match outputs: not the staged pointers");
   }
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   DevFrameView* views = reinterpret_cast<DevFrameView*>(h + st.o_views);
   int ref_levels = 0, max_w = 1, max_h = 1;
   bool pose_from_results = false;
@@ -3847,6 +3851,7 @@ try {
   const size_t n = (size_t)begin[n_lists];
   SVOH_REQUIRE(ctx, n <= ((size_t)1 << 26) && (n == 0 || (cell && success && visited)), "NULL candidate array, or too many candidates");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
   const size_t nl = (size_t)n_lists, nc = (size_t)n_cells;
   // [begin | max_n | num_features | cell | success | occupancy]  up;  [num_features | occupancy | visited | trials | matches | consumed]  back
@@ -3890,6 +3895,7 @@ try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, px && visible && n >= 1 && n == ctx->cand_pending_n, "n is not the number of points of the queued candidate projection");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // returns at once when a fetch of the alignment in front has waited already
   const uint8_t* h = static_cast<const uint8_t*>(ctx->h_cand.ptr) + ctx->cand_out_off;
   memcpy(px, h, sizeof(double) * 2 * (size_t)n);
@@ -3912,6 +3918,7 @@ static int stage_candidates(svoh_ctx* ctx, int n_jobs, int n_kf_total, int n_poi
   SVOH_REQUIRE(ctx, out && n_jobs >= 1 && n_jobs <= 4096 && n_kf_total >= 0 && n_kf_total <= (1 << 20) && n_points_total >= 1 && n_points_total <= (1 << 24), "bad arguments");
   SVOH_REQUIRE(ctx, ctx->cand_stage.state != 2, "a staged candidate projection is in flight: svoh_project_candidates_wait first");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   svoh_ctx::CandStage& st = ctx->cand_stage;
   size_t total = 0;
   auto add = [&](size_t bytes) { const size_t o = total; total = (total + bytes + 63) & ~(size_t)63; return o; };
@@ -3975,6 +3982,7 @@ static int enqueue_staged_candidates(svoh_ctx* ctx, bool with_units)
                "mu_unit: the ranges form only, and a seed batch must have been sent off on this context (its block not laid out anew since)");
   SVOH_REQUIRE(ctx, st.state == 1, "nothing staged (svoh_project_candidates_stage)");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   uint8_t* h = static_cast<uint8_t*>(ctx->h_cand_multi.ptr);
   uint8_t* d = static_cast<uint8_t*>(ctx->d_cand_multi.ptr);
   svoh_candidate_job* jobs = reinterpret_cast<svoh_candidate_job*>(h + st.o_jobs);
@@ -4066,6 +4074,7 @@ try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, ctx->cand_stage.state == 2, "no staged candidate projection in flight");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // returns at once when a fetch of the alignment in front has waited already
   ctx->cand_stage.state = 0;
   return SVOH_OK;
@@ -4079,6 +4088,7 @@ try {
   const int kind = seeds ? 1 : 0;
   SVOH_REQUIRE(ctx, !ctx->matcher_deferred_used[kind], "one batch of each kind per deferred section: collect first");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   svoh_ctx::MatcherStage& st = ctx->matcher_stage[kind];
   SVOH_REQUIRE(ctx, (flags & ~(SVOH_STAGE_MATCH_OUTPUTS | SVOH_STAGE_RESIDENT_COLUMNS)) == 0, "unknown flag");
   if (seeds) ctx->seed_block.valid = false;   // (its uploads are stream-ordered behind whatever still reads the old block)
@@ -4180,6 +4190,7 @@ __global__ void matcher_prologue_kernel(PrologueBatch b0, PrologueBatch b1, int 
 static int launch_deferred(svoh_ctx* ctx)
 {
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   {
     svoh_ctx::DeferredLaunch& d0 = ctx->matcher_deferred_launch[0];
     svoh_ctx::DeferredLaunch& d1 = ctx->matcher_deferred_launch[1];
@@ -4308,6 +4319,7 @@ try {
   const int rc = fill_view(ctx, *cur_frame, &v, "current frame");
   if (rc != SVOH_OK) return rc;
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   // the staged copy is replaced as well: it is the upload's source (pinned: it must keep the bytes until the copy has run)
   DevFrameView* hv = static_cast<DevFrameView*>(dl.views_h) + dl.n_ref;
   *hv = v;

@@ -591,6 +591,7 @@ static int run_pose_batch(svoh_ctx* ctx, const svoh_pose_options* options, int n
   SVOH_REQUIRE(ctx, problems && results, "NULL argument");
   SVOH_REQUIRE(ctx, options->max_iter >= 1 && options->error_type >= 0 && options->error_type <= 2, "bad max_iter / error_type");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
 
   // The wide twin runs a launch whose error type evaluates the camera (UNIT_PLANE uses f and the point only) and in
   // which at least one camera is EQUIDISTANT or ATAN; every other launch runs the narrow kernel.  ATAN has no Jacobian
@@ -831,6 +832,7 @@ static int run_points_batch(svoh_ctx* ctx, bool queued, int n_iter, int using_be
   SVOH_REQUIRE(ctx, n_obs == 0 || (obs_view && obs_f && T_f_w), "NULL observation array");
   for (size_t o = 0; o < n_obs; ++o) SVOH_REQUIRE(ctx, obs_view[o] >= 0 && obs_view[o] < n_views, "observation refers to an unknown view");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
   const size_t o_T = 0, o_begin = al(sizeof(svoh_se3) * (size_t)(n_views ? n_views : 1));
   const size_t o_view = o_begin + al(4 * ((size_t)n_points + 1)), o_f = o_view + al(4 * (n_obs ? n_obs : 1));
@@ -898,6 +900,7 @@ try {
   if (n_points == 0) return SVOH_OK;
   ctx->points_pending = 0;
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
   SVOH_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_points));   // THAT batch: not what the caller has queued on the context since
   const uint8_t* h = static_cast<const uint8_t*>(ctx->h_points_q.ptr);
   memcpy(pos, h + ctx->points_o_pos, 24 * (size_t)n_points);

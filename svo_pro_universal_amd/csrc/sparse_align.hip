@@ -38,6 +38,8 @@
 
 // every wait for the whole stream in this file: the alignment's staging blocks have been read (svoh_internal.h)
 // (and every copy of results that went, or still has to go, over the alignment's copy stream has arrived: align_drain)
+// (and both launch lanes are empty.  SVOH_ALIGN_JOIN, svoh_internal.h, is the wait on the DEVICE that goes with it: the context's
+// stream waits for the launch on the second lane -- what every entry outside enqueue_align does before it uses that stream)
 #define SVOH_ALIGN_DRAIN(ctx) SVOH_HIP_TRY(ctx, svoh::align_drain(ctx))
 
 namespace svoh {
@@ -82,12 +84,35 @@ static hipError_t align_drain(svoh_ctx* ctx)
 {
   hipError_t e = align_flush_download(ctx);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess && ctx->align_lane_stream) e = hipStreamSynchronize(ctx->align_lane_stream);
   if (e == hipSuccess && ctx->align_delivery_pending) e = hipEventSynchronize(ctx->ev_align_delivered);
   if (e != hipSuccess) return e;
+  ctx->align_lane1_pending = false;
+  ctx->align_chain = false;
+  ctx->align_last_lane = 0;
   ctx->align_delivery_pending = false;
   ctx->align_launches_since_drain = 0;
   ctx->align_block_read_ev[0] = ctx->align_block_read_ev[1] = nullptr;
   return hipSuccess;
+}
+
+// Launch lanes (svoh_internal.h): the second lane's stream and its event, made ONCE per context, by its first launch of the kind
+// that can take that lane, queued or not -- for the reason given above for the copy stream: a caller's first such launches are its
+// warm-up, and the runtime sets a stream up when it is first used.  A few bytes of the launch's staged block go up to its device
+// block and come back on the new stream; launches queued ahead are waited for.  (The lane's WORKSPACE is not made here: a context
+// whose launches are never queued behind one another never needs it.)
+static hipError_t align_lane_setup(svoh_ctx* ctx, void* h, void* d, size_t bytes)
+{
+  if (ctx->align_lane_stream) return hipSuccess;
+  hipError_t e = ctx->align_launches_since_drain ? align_drain(ctx) : hipSuccess;
+  if (e == hipSuccess && !ctx->ev_align_lane1) e = hipEventCreateWithFlags(&ctx->ev_align_lane1, hipEventDisableTiming);
+  if (e == hipSuccess && !ctx->ev_align_front) e = hipEventCreateWithFlags(&ctx->ev_align_front, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->align_lane_stream, hipStreamNonBlocking);
+  if (bytes > 4096) bytes = 4096;
+  if (e == hipSuccess) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->align_lane_stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->align_lane_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->align_lane_stream);
+  return e;
 }
 
 struct DevCamDesc {
@@ -2329,7 +2354,6 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
       }
     }
   }
-  SVOH_HIP_TRY(ctx, ctx->d_feat.reserve(feat_slots * (kWsPairs * 16 + 2) + 256));
   SVOH_HIP_TRY(ctx, ctx->d_eval.reserve(74 * sizeof(double) * S));
 
   DevProblemDesc* hp = static_cast<DevProblemDesc*>(h_desc.ptr);
@@ -2436,13 +2460,58 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   const bool side_kind = n_desc >= ctx->num_cus && !cluster && !split && !forced && eval_level < 0 &&
                          (side_knob == kKnobUnset ? up_base + up_off > ((size_t)1 << 20) : side_knob != 0);
   if (side_kind) SVOH_HIP_TRY(ctx, align_side_setup(ctx, h_desc.ptr, d_desc.ptr, up_base + up_off));
+  // Launch lanes (svoh_internal.h).  A launch of the batch geometry -- the 256-thread batch build over at least a workgroup per
+  // compute unit; not a cluster, keyed, split or evaluation launch, none whose seed positions are gathered on the context's stream --
+  // that comes right behind another such launch nobody has waited for, with nothing put on the context's stream in between
+  // (align_chain), takes the lane that launch did not take: its kernel starts as soon as compute units of the previous kernel
+  // fall idle.  Everything else runs on lane 0, the context's stream, behind whatever runs on lane 1.
+  // SVOH_ALIGN_OVERLAP=0: one lane.  On by default at every size of the batch geometry: 512 ... 4096 frame pairs per step all gain
+  // (0.52 against 0.71 ms per step, 0.96 against 1.17, 2.03 against 2.21, 3.42 against 3.74: profiles/r08_align_overlap_ab.txt).
+  const AlignGeometry geo = forced ? *forced : decide_geometry(ctx, opt, n_desc, cluster ? S : 0, shape);
+  const int overlap_knob = ctx->knobs.align_overlap;
+  const bool lane_kind = n_desc >= ctx->num_cus && geo.nt == 256 && !geo.latency && !cluster && !split && !forced && eval_level < 0 && n_pos_jobs == 0 &&
+                         (overlap_knob == kKnobUnset || overlap_knob != 0);
+  if (lane_kind) SVOH_HIP_TRY(ctx, align_lane_setup(ctx, h_desc.ptr, d_desc.ptr, up_base + up_off));
+  const size_t feat_bytes = feat_slots * (kWsPairs * 16 + 2) + 256;
+  {
+    // A lane's workspace grows as the single one did, sized by the largest launch the lane has seen; the second lane's is made by
+    // the context's first launch that takes that lane.  While one that is in use is replaced nothing runs on either lane (the
+    // launch is then the first of a new queue, on lane 0; the workspace it was headed for has grown all the same, for the next).
+    const bool to_lane1 = lane_kind && ctx->align_chain && ctx->align_launches_since_drain >= 1 && ctx->align_last_lane == 0;
+    DevBuffer& ws = to_lane1 ? ctx->d_feat_lane1 : ctx->d_feat;
+    if (ws.ptr && feat_bytes > ws.cap && ctx->align_launches_since_drain >= 1 && ctx->align_lane_stream && ctx->align_lane1_launches) {
+      SVOH_ALIGN_DRAIN(ctx);
+      SVOH_HIP_TRY(ctx, ws.reserve(feat_bytes));
+    }
+  }
+  // (the last wait for the stream of this call lies behind: what follows is this launch's place in the queue)
+  const bool overlapped = lane_kind && ctx->align_chain && ctx->align_launches_since_drain >= 1;   // runs beside the launch before it
+  const int lane = overlapped ? (ctx->align_last_lane ^ 1) : 0;
+  DevBuffer& d_feat = lane ? ctx->d_feat_lane1 : ctx->d_feat;
+  SVOH_HIP_TRY(ctx, d_feat.reserve(feat_bytes));
+  const hipStream_t prev_stream = ctx->align_stream_of(ctx->align_last_lane);   // where the launch before this one runs
+  if (lane) {
+    // whatever was on the context's stream before the queue began stays in front of the second lane as well
+    if (ctx->align_lane1_wants_front) {
+      SVOH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->align_lane_stream, ctx->ev_align_front, 0));
+      ctx->align_lane1_wants_front = false;
+    }
+  } else if (!overlapped) {
+    // the context's stream waits for the second lane, as in every other entry that puts work on it
+    SVOH_ALIGN_JOIN(ctx);
+    if (lane_kind) {   // the launch behind this one may take the second lane: what is on the stream now lies in front of that one too
+      SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_front, ctx->stream));
+      ctx->align_lane1_wants_front = true;
+    }
+  }
+  const hipStream_t ks = ctx->align_stream_of(lane);
   const bool side = side_kind && ctx->align_launches_since_drain >= 1;
   const unsigned prev_slot = desc_slot ^ 1u;
   if (side) {
     // what this launch does not read must not wait behind it: the launch before this one, if it kept to the context's stream,
     // has no event behind its kernel yet (the launch after this one will upload into its block)
     if (!ctx->align_block_read_ev[prev_slot]) {
-      SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_kernel[prev_slot], ctx->stream));
+      SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_kernel[prev_slot], prev_stream));
       ctx->align_block_read_ev[prev_slot] = ctx->ev_align_kernel[prev_slot];
     }
     // the kernel of the launch before the last one may still read this device block
@@ -2450,7 +2519,7 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
     SVOH_HIP_TRY(ctx, hipMemcpyAsync(d_desc.ptr, h_desc.ptr, up_base + up_off, hipMemcpyHostToDevice, ctx->align_copy_stream));
     SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_uploaded, ctx->align_copy_stream));
     // what the host waits for before it writes the OTHER pinned block again lies behind the upload that last read that block,
-    // the previous launch's: on the copy stream if it went there, else behind that launch's kernel on the context's stream
+    // the previous launch's: on the copy stream if it went there, else behind that launch's kernel on its lane
     if (ctx->align_last_was_side) {
       SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_staged, ctx->align_copy_stream));
       ctx->align_staged_wait_ev = ctx->ev_align_staged;
@@ -2458,11 +2527,16 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
       ctx->align_staged_wait_ev = ctx->align_block_read_ev[prev_slot];
     }
     SVOH_HIP_TRY(ctx, align_flush_download(ctx));   // the previous launch's results: behind this upload, beside this kernel
-    SVOH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_align_uploaded, 0));
+    SVOH_HIP_TRY(ctx, hipStreamWaitEvent(ks, ctx->ev_align_uploaded, 0));
     ++ctx->align_side_launches;
   } else {
     SVOH_HIP_TRY(ctx, align_flush_download(ctx));
-    SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d_desc.ptr, h_desc.ptr, up_base + up_off));
+    // An overlapped launch that keeps its copies on its lane: the launch before it runs on the other lane, so nothing on this
+    // lane says that its upload has read the other pinned block.  What the host waits for before it writes that block again
+    // (and before the launch after this one uploads into that launch's device block, in-stream or on the copy stream) is
+    // recorded behind that launch's kernel instead.
+    if (overlapped) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_staged, prev_stream));
+    SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d_desc.ptr, h_desc.ptr, up_base + up_off, ks));
   }
   if (pos_jobs_device) {
     const int rcp = svoh_launch_pos_from_seed_batch(ctx, (int)pos_jobs.size(), pos_jobs_max_n, pos_jobs_device);
@@ -2472,19 +2546,22 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   if (!side) {
     ctx->align_staged_wait_ev = nullptr;
     if (ctx->align_launches_since_drain >= 1) {   // queued behind a launch nobody has waited for: the next one may need this
-      SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_staged, ctx->stream));
+      if (!overlapped) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_staged, ks));   // (overlapped: recorded above, behind the previous kernel)
       ctx->align_staged_wait_ev = ctx->ev_align_staged;
     }
     ctx->align_block_read_ev[desc_slot] = nullptr;   // (an event of an earlier kernel on this block says nothing about this one)
   }
   ctx->align_last_was_side = side;
   ++ctx->align_launches_since_drain;
+  ctx->align_last_lane = lane;
+  ctx->align_chain = lane_kind;   // (a launch of another kind on the context's stream ends the queue like any other work there)
+  if (lane) ++ctx->align_lane1_launches;
 
   AlignKernelArgs args;
   args.problems = static_cast<const DevProblemDesc*>(d_desc.ptr);
   args.cams = reinterpret_cast<const DevCamDesc*>(args.problems + n_desc);
   args.results = static_cast<svoh_align_result*>(ctx->d_results.ptr) + dev_results_off;
-  double* w = static_cast<double*>(ctx->d_feat.ptr);
+  double* w = static_cast<double*>(d_feat.ptr);
   args.wpk = w;
   args.slots = (int64_t)feat_slots;
   args.wsel = reinterpret_cast<uint8_t*>(w + 2 * kWsPairs * feat_slots);
@@ -2534,8 +2611,7 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   args.stamps = static_cast<long long*>(ctx->d_scratch0.ptr);
 #endif
 
-  // geometry (decide_geometry): chosen from the launch, or the caller's (a keyed launch: the geometry of a problem alone)
-  const AlignGeometry geo = forced ? *forced : decide_geometry(ctx, opt, n_desc, cluster ? S : 0, shape);
+  // geometry (decide_geometry, above): chosen from the launch, or the caller's (a keyed launch: the geometry of a problem alone)
   const int nt = geo.nt, rows = geo.rows;
   // 256 threads: two workgroups per CU, each with <= 29 KB of static LDS (reduction scratch, the 24 KB LDS-DMA staging
   // area of the workspace rows) -> 51 KB for images: levels 4, 3 and 2 of a 640x480 pyramid side by side (50 400 B);
@@ -2565,20 +2641,20 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   hipError_t e;
   const bool timed = ctx->timing_on();
   const int ev_slot = (int)(ctx->align_timed_launches % svoh_ctx::kAlignEventRing);
-  if (timed) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_start[ev_slot], ctx->stream));
+  if (timed) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_start[ev_slot], ks));
   const bool robust = opt->robustification != 0;
   int32_t lds_img_launched = 0;
 #ifdef SVOH_DEV_ONLY_PLAIN   // development builds only (scripts/kernel_resources.sh, quick A/B libraries): the 4x4 / 8x8 kernels without illumination terms and robust weights
   if (robust || illum) return set_error(ctx, SVOH_ERR_UNSUPPORTED, "development build: plain kernels only");
-  e = opt->patch_size == 4 ? launch_nt<4, false, false>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched)
-                           : launch_nt<8, false, false>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched);
+  e = opt->patch_size == 4 ? launch_nt<4, false, false>(ks, nt, rows, grid, lds, args, &lds_img_launched)
+                           : launch_nt<8, false, false>(ks, nt, rows, grid, lds, args, &lds_img_launched);
 #else
   if (opt->patch_size == 4) {
-    if (robust) e = illum ? launch_nt<4, true, true>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched) : launch_nt<4, false, true>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched);
-    else e = illum ? launch_nt<4, true, false>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched) : launch_nt<4, false, false>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched);
+    if (robust) e = illum ? launch_nt<4, true, true>(ks, nt, rows, grid, lds, args, &lds_img_launched) : launch_nt<4, false, true>(ks, nt, rows, grid, lds, args, &lds_img_launched);
+    else e = illum ? launch_nt<4, true, false>(ks, nt, rows, grid, lds, args, &lds_img_launched) : launch_nt<4, false, false>(ks, nt, rows, grid, lds, args, &lds_img_launched);
   } else {
-    if (robust) e = illum ? launch_nt<8, true, true>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched) : launch_nt<8, false, true>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched);
-    else e = illum ? launch_nt<8, true, false>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched) : launch_nt<8, false, false>(ctx->stream, nt, rows, grid, lds, args, &lds_img_launched);
+    if (robust) e = illum ? launch_nt<8, true, true>(ks, nt, rows, grid, lds, args, &lds_img_launched) : launch_nt<8, false, true>(ks, nt, rows, grid, lds, args, &lds_img_launched);
+    else e = illum ? launch_nt<8, true, false>(ks, nt, rows, grid, lds, args, &lds_img_launched) : launch_nt<8, false, false>(ks, nt, rows, grid, lds, args, &lds_img_launched);
   }
 #endif
   if (e != hipSuccess)
@@ -2589,18 +2665,19 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
     const hipError_t es = hipGetLastError();
     if (es != hipSuccess) return set_error(ctx, SVOH_ERR_HIP, "sum_shares launch failed: %s", hipGetErrorString(es));
   }
-  if (timed) { SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_stop[ev_slot], ctx->stream)); ++ctx->align_timed_launches; }
+  if (timed) { SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_stop[ev_slot], ks)); ++ctx->align_timed_launches; }
   ctx->align_last_timed = timed;
   ++ctx->align_launches;
   if (!split && eval_level < 0) {   // svoh_sparse_align_last_launch_info
     ctx->align_last_geometry_key = geo.key(); ctx->align_last_grid = grid; ctx->align_last_n_desc = n_desc;
     ctx->align_last_lds_img_bytes = lds_img_launched;
   }
+  ctx->align_last_info_lane = lane;   // svoh_sparse_align_last_launch_lane: of every launch, evaluations included
   // the results follow the kernel to pinned host memory right away, so that a caller which queues several
   // launches and fetches once still has every launch's output delivered
   if (side) {
     // behind this kernel: the copy stream may write this device block again (the launch after the next), and take the results
-    SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_kernel[desc_slot], ctx->stream));
+    SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_kernel[desc_slot], ks));
     ctx->align_block_read_ev[desc_slot] = ctx->ev_align_kernel[desc_slot];
     // held back until the next launch has queued its upload, or somebody drains (align_flush_download)
     ctx->align_download.dst = static_cast<svoh_align_result*>(ctx->h_results.ptr) + ctx->align_pending_results;
@@ -2611,7 +2688,7 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   if (delivers) {   // cluster: entry 0 is share 0's copy of the common result
     if (!side)
       SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, static_cast<svoh_align_result*>(ctx->h_results.ptr) + ctx->align_pending_results,
-                                          args.results, sizeof(svoh_align_result) * n_problems));
+                                          args.results, sizeof(svoh_align_result) * n_problems, ks));
     ctx->align_last_results_off = ctx->align_pending_results;
     // where on the device result #k of the queue lives (svoh_project_candidates_enqueue's align_result_index)
     if (ctx->align_pending_results == 0) ctx->align_result_dev_index.clear();
@@ -2619,10 +2696,15 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
     ctx->align_pending_results += (size_t)n_problems;
     ctx->align_pending_dev = dev_results_off + (size_t)n_desc + (size_t)n_problems;
   }
+  // the second lane's launch is what the context's stream has to wait for before anything else uses its results or its inputs
+  if (lane) {
+    SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_lane1, ks));
+    ctx->align_lane1_pending = true;
+  }
 #ifdef SVOH_PHASE_STAMPS
   {
     std::vector<long long> h((size_t)n_problems * 20);
-    SVOH_HIP_TRY(ctx, hipMemcpyAsync(h.data(), args.stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    SVOH_HIP_TRY(ctx, hipMemcpyAsync(h.data(), args.stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost, ks));
     SVOH_ALIGN_DRAIN(ctx);
     double sum[20] = {0};
     for (int p = 0; p < n_problems; ++p) for (int k = 0; k < 20; ++k) sum[k] += (double)h[(size_t)p * 20 + k];
@@ -2674,6 +2756,7 @@ int svoh_set_align_geometry_classes(svoh_ctx* ctx, int shared)
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, shared == 0 || shared == 1, "geometry classes: 0 = the fastest geometry for a problem alone, 1 = shared classes");
+  if (ctx->align_launches_since_drain && ctx->align_lane_stream) SVOH_ALIGN_DRAIN(ctx);   // the geometry of launches is planned anew: both lanes run empty first
   ctx->align_shared_classes = shared != 0;
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
@@ -2772,6 +2855,17 @@ try {
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
 
+int svoh_sparse_align_last_launch_lane(svoh_ctx* ctx, int32_t* lane, int32_t* lanes, uint64_t* lane1_launches)
+try {
+  if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  SVOH_REQUIRE(ctx, lane && lanes, "NULL argument");
+  SVOH_REQUIRE(ctx, ctx->align_launches != 0, "no alignment launch on this context yet");
+  *lane = ctx->align_last_info_lane;
+  *lanes = ctx->align_lane_stream ? 2 : 1;
+  if (lane1_launches) *lane1_launches = ctx->align_lane1_launches;
+  return SVOH_OK;
+} SVOH_ABI_CATCH(ctx)
+
 int svoh_sparse_align_last_launch_lds(svoh_ctx* ctx, int32_t* lds_img_bytes)
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
@@ -2853,6 +2947,7 @@ try {
   h.T_old = problem->T_icur_iref;
   h.alpha = h.alpha_old = problem->alpha_init;
   h.beta = h.beta_old = problem->beta_init;
+  SVOH_ALIGN_JOIN(ctx);
   SVOH_HIP_TRY(ctx, hipMemcpyAsync(d_state, &h, sizeof h, hipMemcpyHostToDevice, ctx->stream));
   SVOH_ALIGN_DRAIN(ctx);   // h is a stack object
   return SVOH_OK;

@@ -204,6 +204,7 @@ struct SvohKnobs {
   int kernel_timing = kKnobUnset;             // SVOH_KERNEL_TIMING: 1 = bracket every kernel with an event pair (svoh_set_kernel_timing)
   int copy_kernel = kKnobUnset;               // SVOH_COPY_KERNEL / svoh_set_copy_policy: 0 = staged blocks through hipMemcpyAsync, 1 (default) = copy kernels for 16 KB .. 1 MB, 2 = copy kernels always
   int align_side_copies = kKnobUnset;         // SVOH_ALIGN_SIDE_COPIES: 0 = a queued batch launch of the alignment keeps its copies on the context's stream (A/B), 1 = every one takes the copy stream; unset = those whose block is larger than 1 MB
+  int align_overlap = kKnobUnset;             // SVOH_ALIGN_OVERLAP: 0 = every alignment launch on the context's stream (one lane), 1 or unset = a launch of the batch geometry queued right behind another takes the other lane
   static int or_default(int v, int dflt) { return v == kKnobUnset ? dflt : v; }
 };
 void load_knobs_from_env(SvohKnobs& k);
@@ -281,6 +282,27 @@ struct svoh_ctx {
   bool align_delivery_pending = false;        // ev_align_delivered lies behind copies to h_results that nobody has waited for
   bool align_last_was_side = false;           // the most recent launch uploaded on the copy stream
   unsigned long long align_side_launches = 0; // launches that took the side path (read by svoh_test_align_side_launches of libsvo_hip_testhooks.so only)
+  // Launch lanes (sparse_align.hip, enqueue_align; SVOH_ALIGN_OVERLAP=0 turns them off).  A launch of the batch geometry queued
+  // right behind another one that nobody has waited for runs on the OTHER lane: its workgroups become resident one by one, as the
+  // workgroups of the launch before it leave their compute units, instead of all together once that launch has ended.  Lane 0 is
+  // `stream` with `d_feat`, lane 1 align_lane_stream with d_feat_lane1 (each lane's kernels follow one another in stream order, so a
+  // lane's workspace has one user at a time; the queue head of a launch lies in its descriptor block, and launches that follow one
+  // another never share a block).  Two launches on different lanes share nothing but read-only inputs.
+  //   ctx->stream:  record(ev_align_front)  [upload N]  kernel N                         kernel N+2
+  //   lane 1:       wait(ev_align_front)                 [upload N+1]  kernel N+1  record(ev_align_lane1)
+  // Everything else that puts work on `stream`, or hands `stream` out, calls align_join_lanes first: `stream` then waits for lane 1,
+  // and the next batch launch is the first of a new queue -- on lane 0, behind whatever was put there.
+  hipStream_t align_lane_stream = nullptr;    // made, like d_feat_lane1, by the context's first launch that takes lane 1
+  svoh::DevBuffer d_feat_lane1;
+  hipEvent_t ev_align_front = nullptr;        // on `stream` in front of the first launch of a queue: what was there before it
+  hipEvent_t ev_align_lane1 = nullptr;        // on lane 1 behind its most recent launch
+  bool align_lane1_pending = false;           // ... which `stream` has not waited for (and no host wait has covered)
+  bool align_lane1_wants_front = false;       // ev_align_front was recorded and lane 1 has not waited for it yet
+  bool align_chain = false;                   // the most recent work on either lane is a launch of the batch geometry that may be overlapped
+  int align_last_lane = 0;                    // the lane of the most recent alignment launch
+  unsigned long long align_lane1_launches = 0;
+  int32_t align_last_info_lane = 0;           // svoh_sparse_align_last_launch_lane: the lane of the most recent launch of the resident kernel (full run or evaluation)
+  hipStream_t align_stream_of(int lane) const { return lane ? align_lane_stream : stream; }
   bool align_shared_classes = false;   // svoh_set_align_geometry_classes
   bool align_no_cluster = false;   // svoh_sparse_align_batch repeating a launch whose cluster gave up
   hipEvent_t ev_misc_start = nullptr, ev_misc_stop = nullptr;  // KLT / matcher / seeds
@@ -395,11 +417,24 @@ int reserve_unit_counts(svoh_ctx* ctx, size_t n_units, unsigned int** out);
 // (tools/svoh_call_overhead, h2d_kernel_copykernel_sync against h2d_kernel_d2h_sync: 32 KB 20.6 / 24.2 us, 128 KB
 // 23.4 / 28.4; 4 KB 18.4 / 16.5 the other way round): blocks of 16 KB .. 1 MB, 16-byte aligned, go through a copy
 // kernel, everything else through hipMemcpyAsync.  SVOH_COPY_KERNEL=0: always hipMemcpyAsync.
-hipError_t svoh_copy_to_host(svoh_ctx* ctx, void* dst_pinned, const void* src_device, size_t bytes);
+// (`on`: another stream than the context's -- the alignment's second lane)
+hipError_t svoh_copy_to_host(svoh_ctx* ctx, void* dst_pinned, const void* src_device, size_t bytes, hipStream_t on = nullptr);
 // The other direction: a staged input block from PINNED host memory to the device.  Same finding (h2d_kernel_d2h_sync
 // against copyin_kernel_d2h_sync with SVOH_OVERHEAD_N_IN): 32 KB 27.4 / 24.7 us, 64 KB 33.7 / 29.0, 128 KB 48.8 / 37.9; 16 KB
 // 18.1 / 22.6 the other way round -- blocks of 32 KB .. 1 MB are read by a copy kernel, the rest goes through hipMemcpyAsync.
-hipError_t svoh_copy_to_device(svoh_ctx* ctx, void* dst_device, const void* src_pinned, size_t bytes);
+hipError_t svoh_copy_to_device(svoh_ctx* ctx, void* dst_device, const void* src_pinned, size_t bytes, hipStream_t on = nullptr);
+// Launch lanes of the alignment (svoh_ctx): called by every entry that puts work on the context's stream, or hands that stream out,
+// before it does.  The stream waits for the launch on lane 1, if there is one it has not waited for, and the queue of overlapped
+// launches ends: the next alignment launch goes onto the context's stream, behind the caller's work.  Two flag tests when there is
+// nothing to join.
+inline hipError_t align_join_lanes(svoh_ctx* ctx)
+{
+  ctx->align_chain = false;
+  if (!ctx->align_lane1_pending) return hipSuccess;
+  const hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->ev_align_lane1, 0);
+  if (e == hipSuccess) ctx->align_lane1_pending = false;
+  return e;
+}
 int reduce_unit_counts(svoh_ctx* ctx, size_t n_units);
 void set_global_error(const char* msg);
 const Frame* find_frame(const svoh_ctx* ctx, svoh_frame_t id);
@@ -438,6 +473,8 @@ __device__ __forceinline__ int wave_sum_i32_dpp(int v)
       return svoh::set_error((ctx), SVOH_ERR_HIP, "%s failed: %s (%s:%d)", #expr,        \
                              hipGetErrorString(svoh_e_), __FILE__, __LINE__);            \
   } while (0)
+
+#define SVOH_ALIGN_JOIN(ctx) SVOH_HIP_TRY(ctx, svoh::align_join_lanes(ctx))
 
 #define SVOH_REQUIRE(ctx, cond, msg)                                                     \
   do {                                                                                   \

@@ -243,6 +243,13 @@ class Context(object):
         return dict(key=k, cluster_g=k & 0xff, nt=512 if (k >> 8) & 1 else 256, rows=(k >> 9) & 0xf,
                     latency=bool((k >> 13) & 1), rig=bool((k >> 14) & 1), grid=grid.value, n_desc=n_desc.value)
 
+    def last_align_lane(self):
+        """svoh_sparse_align_last_launch_lane: dict(lane, lanes, lane1_launches) -- the launch lane of the most recent alignment
+        launch, how many lanes the context has, how many of its launches took the second one."""
+        lane, lanes, n1 = C.c_int32(), C.c_int32(), C.c_uint64()
+        self._check(self.lib.svoh_sparse_align_last_launch_lane(self.h, C.byref(lane), C.byref(lanes), C.byref(n1)))
+        return dict(lane=lane.value, lanes=lanes.value, lane1_launches=int(n1.value))
+
     def last_align_launch_lds(self):
         """svoh_sparse_align_last_launch_lds: the LDS bytes the most recent full-run alignment launch had for the levels' images."""
         n = C.c_int32()
