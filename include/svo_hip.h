@@ -828,6 +828,37 @@ int svoh_update_seeds_batch_ex(svoh_ctx* ctx, const svoh_matcher_options* matche
                                double* state, uint8_t* success, int32_t* match_result,
                                int32_t* n_success, const svoh_seed_match_outputs* outputs);
 
+/* The seeds of new keyframes against a LIST of frames each, in one launch: what FrameHandlerMono::processFrame does
+ * right after depth_filter_->addKeyframe when update_seeds_with_old_keyframes is set (frame_handler_mono.cpp:218-225:
+ * updateSeeds({new keyframe}, last frame), then the same with every overlap keyframe in turn).  Equivalent, bit for bit,
+ * to one svoh_update_seeds_batch call per list position: every unit walks the list of its reference frame on the device,
+ * state and type carried from step to step (the search range of a step comes from the sigma2 the step before left; a
+ * seed that converges goes on as a converged seed, one that becomes an outlier is skipped from then on).
+ * Host arrays only: features->mem_space = SVOH_MEM_HOST, layout SVOH_BATCH_UNITS, cur_frame_idx and feature_index NULL.
+ * The seeds of reference frame r walk chain_frames[chain_idx[k]] for k = chain_begin[r] .. chain_begin[r + 1] - 1, in
+ * that order (chain_begin: n_ref_frames + 1 entries, non-decreasing from 0; a frame may stand in several chains, and
+ * twice in one).  state (4 x n) and features->type are updated in place.
+ * Outputs: *n_success (may be NULL) = successes summed over all steps, what the calls of updateSeeds would have summed;
+ * steps_succeeded[n] (required); step_result / step_success (n x max_steps, entry [i * max_steps + j] = unit i at list
+ * position j, either may be NULL): svoh_match_result and updateSeed's return value of every step, SVOH_MATCH_NOT_RUN / 0
+ * beyond a unit's chain.  max_steps is read only when one of the two is given.
+ * Refused before anything is staged, the context staying usable: chain_begin not non-decreasing from 0, a chain_idx
+ * outside [0, n_chain_frames), an unknown frame handle (SVOH_ERR_BAD_HANDLE), a camera that is not the frame's size, a
+ * wide distortion model (SVOH_ERR_UNSUPPORTED), max_steps smaller than the longest chain while step outputs are asked for.
+ * n == 0 or no chain entries at all: SVOH_OK without a launch, zeros (SVOH_MATCH_NOT_RUN) in the outputs.
+ * The call blocks.  It stages through buffers of its own: like svoh_epipolar_match_batch it is allowed inside an open
+ * deferred section, also while a flushed seed batch is in flight, and leaves the section's batches intact.  Small
+ * batches' geometries only (SVOH_MATCHER_G8 = 0 one lane, 1 eight lanes -- the default --, 3 one wave per unit; 2 runs
+ * eight lanes). */
+int svoh_update_seeds_chain(svoh_ctx* ctx, const svoh_matcher_options* matcher_options,
+                            const svoh_depth_filter_options* options,
+                            int n_ref_frames, const svoh_frame_view* ref_frames,
+                            const svoh_feature_batch* features, double* state,
+                            int n_chain_frames, const svoh_frame_view* chain_frames,
+                            const int32_t* chain_begin, const int32_t* chain_idx,
+                            int32_t* n_success, int32_t* steps_succeeded,
+                            int32_t* step_result, uint8_t* step_success, int max_steps);
+
 /* ---- stereo seam: plain epipolar matches with their triangulated depth ---- */
 
 /* Per-feature outputs of svoh_epipolar_match_batch: what Matcher::findEpipolarMatchDirect

@@ -299,7 +299,7 @@ EXPORTS = [
     "svoh_sparse_align_split_buffers", "svoh_sparse_align_split_init", "svoh_sparse_align_partial_sums", "svoh_sparse_align_gn_update",
     "svoh_klt_track_batch", "svoh_klt_track_multi", "svoh_klt_track_indexed", "svoh_last_kernel_ms", "svoh_last_kernel_counters",
     "svoh_match_direct_batch", "svoh_match_direct_batch_pixelwise", "svoh_matcher_begin_deferred", "svoh_matcher_collect", "svoh_matcher_flush", "svoh_matcher_deferred_set_cur_frame", "svoh_optimize_pose_batch_hook",
-    "svoh_update_seeds_batch", "svoh_update_seeds_batch_ex", "svoh_epipolar_match_batch",
+    "svoh_update_seeds_batch", "svoh_update_seeds_batch_ex", "svoh_update_seeds_chain", "svoh_epipolar_match_batch",
     "svoh_project_candidates_enqueue", "svoh_project_candidates_collect", "svoh_project_candidates",
     "svoh_detect_features", "svoh_optimize_pose_batch", "svoh_optimize_pose_batch_packed", "svoh_optimize_points_batch", "svoh_optimize_points_batch_enqueue", "svoh_optimize_points_batch_collect",
     # round 5: what the lock-step front end of many camera streams stages in place and launches once per stage
@@ -439,6 +439,9 @@ def load(path=None):
     lib.svoh_optimize_pose_batch_packed.argtypes = [C.c_void_p, P(svoh_pose_options), C.c_int, P(svoh_pose_problem),
                                                     P(svoh_pose_packed_arrays), P(svoh_pose_result)]
     lib.svoh_update_seeds_batch_ex.argtypes = lib.svoh_update_seeds_batch.argtypes + [P(svoh_seed_match_outputs)]
+    lib.svoh_update_seeds_chain.argtypes = [C.c_void_p, P(svoh_matcher_options), P(svoh_depth_filter_options), C.c_int,
+                                            P(svoh_frame_view), P(svoh_feature_batch), C.c_void_p, C.c_int, P(svoh_frame_view),
+                                            C.c_void_p, C.c_void_p, P(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.svoh_epipolar_match_batch.argtypes = [C.c_void_p, P(svoh_matcher_options), C.c_int, P(svoh_frame_view),
                                               P(svoh_frame_view), P(svoh_se3), P(svoh_feature_batch), P(C.c_double),
                                               C.c_void_p, P(svoh_epipolar_match_outputs)]

@@ -2097,6 +2097,129 @@ __global__ __launch_bounds__(64) void match_mixed_kernel(const MatcherArgs ad, c
   else update_seeds_body<G8 ? 1 : 0>(as, (int)blockIdx.x - n_blocks_direct, s_pwb);
 }
 
+// ---- a new keyframe's seeds against a list of frames (svoh_update_seeds_chain) --------------------------------------------
+// FrameHandlerMono::processFrame with update_seeds_with_old_keyframes (frame_handler_mono.cpp:218-225): right after
+// addKeyframe the fresh seeds are updated with the last frame and then with every overlap keyframe in turn.  Per seed that
+// is a dependent chain -- the search range of step j + 1 comes from the sigma2 step j left, and the type may change in
+// between -- and the seeds do not interact: every unit walks the frame list of its reference frame here, state and type
+// in registers, instead of one launch and one round trip per list entry.  One step is what update_seeds_body does to the
+// unit with that current frame, in the same order and with the same operations (the lanes of a unit all compute the
+// same, so every lane carries the state to the next step; one of them reports).
+struct SeedChainArgs {
+  const int32_t* chain_begin;   // n_ref_frames + 1: the units of reference frame r walk chain_idx[chain_begin[r] .. chain_begin[r + 1])
+  const int32_t* chain_idx;     // indices into MatcherArgs::cur_frame (n_cur_frames of them); validated by the host
+  int32_t* steps_succeeded;     // n
+  int32_t* step_result;         // n x max_steps, or NULL
+  uint8_t* step_success;        // n x max_steps, or NULL
+  int max_steps;
+};
+
+// one step: returns updateSeed's return value; res = the matcher's result, or SVOH_MATCH_NOT_RUN when the step returned before it
+template <int G8>
+__device__ __forceinline__ bool update_seed_chain_step(const MatcherArgs& a, MatcherState& m, const DevFrameView& ref, const DevFrameView& cur,
+                                                       double pxr, double pyr, const Vec3& f, double gx, double gy, int level,
+                                                       double (&st)[4], int& type, int& res)
+{
+  res = SVOH_MATCH_NOT_RUN;
+  if (!(type < 6)) return false;  // isSeed
+  double cur_thresh = a.dopt.seed_convergence_sigma2_thresh;
+  if (type == SVOH_FT_MAPPOINT_SEED || type == SVOH_FT_MAPPOINT_SEED_CONVERGED)
+    cur_thresh = a.dopt.mappoint_convergence_sigma2_thresh;
+  if (cur.id == ref.id) return false;
+  if (type == SVOH_FT_OUTLIER) return false;
+  if ((type == SVOH_FT_CORNER_SEED_CONVERGED || type == SVOH_FT_EDGELET_SEED_CONVERGED ||
+       type == SVOH_FT_MAPPOINT_SEED_CONVERGED) && a.dopt.check_convergence)
+    return false;
+  const Rigid T_cur_ref = T_cur_ref_of(ref, cur);
+  if (a.dopt.check_visibility) {
+    const double depth = 1.0 / st[0];
+    const Vec3 p = { depth * f.x, depth * f.y, depth * f.z };
+    double px, py;
+    project3(cur.cam, transform(T_cur_ref, p), px, py);
+    if (!(px >= 0.0 && py >= 0.0 && px < (double)cur.cam.width && py < (double)cur.cam.height)) return false;
+    const int pxi0 = (int)px, pxi1 = (int)py;
+    const int boundary = 9;
+    if (!(pxi0 >= boundary && pxi1 >= boundary && pxi0 < cur.cam.width - boundary && pxi1 < cur.cam.height - boundary)) return false;
+  }
+  // a fresh Matcher per updateSeed, as in update_seeds_body (the work counters run on)
+  m.h_inv = 0.0; m.search_level = 0; m.reject = false;
+  m.align_1d = (type == SVOH_FT_EDGELET_SEED || type == SVOH_FT_EDGELET_SEED_CONVERGED);
+  m.A[0] = m.A[1] = m.A[2] = m.A[3] = 0.0;
+  m.px_cur[0] = m.px_cur[1] = 0.0;
+  m.f_cur = { 0.0, 0.0, 0.0 };
+  double depth = 0.0;
+  const double inv_min = st[0] + sqrt(st[1]);
+  const double inv_max = fmax(st[0] - sqrt(st[1]), 0.00000001);
+  res = find_epipolar_match_direct<G8>(m, a.mopt, ref, cur, T_cur_ref, pxr, pyr, f, gx, gy, level, type, st[0], inv_min, inv_max, depth);
+  if (res != SVOH_MATCH_SUCCESS) {
+    if (!m.reject) st[3] = st[3] + 1;  // seed::increaseOutlierProbability
+    return false;
+  }
+  const double depth_sigma = compute_tau(inverse(T_cur_ref), f, depth, a.dopt.px_error_angle);
+  const double z = 1.0 / depth;
+  const double sg = 0.5 * (1.0 / fmax(0.000000000001, depth - depth_sigma) - 1.0 / (depth + depth_sigma));
+  const double tau2 = sg * sg;
+  bool ok;
+  if (a.dopt.use_vogiatzis_update) ok = update_filter_vogiatzis(z, tau2, ref.seed_mu_range, st);
+  else ok = update_filter_gaussian(z, tau2, st);
+  if (!ok) { type = SVOH_FT_OUTLIER; return false; }
+  const double thresh = ref.seed_mu_range / cur_thresh;
+  if (st[1] < thresh * thresh) {
+    if (type == SVOH_FT_CORNER_SEED) type = SVOH_FT_CORNER_SEED_CONVERGED;
+    else if (type == SVOH_FT_EDGELET_SEED) type = SVOH_FT_EDGELET_SEED_CONVERGED;
+    else if (type == SVOH_FT_MAPPOINT_SEED) type = SVOH_FT_MAPPOINT_SEED_CONVERGED;
+  }
+  return true;
+}
+
+// G8: 0 one lane per unit, 1 eight lanes per unit, 3 one wave per unit, as update_seeds_kernel
+template <int G8>
+__global__ __launch_bounds__(64) void update_seeds_chain_kernel(const MatcherArgs a, const SeedChainArgs c)
+{
+  __shared__ __attribute__((aligned(16))) unsigned char s_pwb[64 * kPwbStride];
+  const int unit = G8 == 1 ? (int)(threadIdx.x >> 3) : (G8 == 3 ? 0 : (int)threadIdx.x);
+  const int i = (int)blockIdx.x * (G8 == 1 ? 8 : (G8 == 3 ? 1 : 64)) + unit;
+  if (i >= a.n) return;
+  const bool reporter = G8 == 0 || (G8 == 1 && (threadIdx.x & 7) == 0) || (G8 == 3 && (threadIdx.x & 63) == 0);
+  // (host arrays only: reference index, level and the chains were validated before anything was staged)
+  const int ri = a.ref_frame_idx[i];
+  const DevFrameView& ref = a.ref_frames[ri];
+  const int jb = c.chain_begin[ri];
+  const int len = c.chain_begin[ri + 1] - jb;   // the loop bound: what the host validated
+  int type = a.type[i];
+  double st[4] = { a.state[4 * i], a.state[4 * i + 1], a.state[4 * i + 2], a.state[4 * i + 3] };
+  MatcherState m;
+  m.pwb = s_pwb + unit * kPwbStride;
+  m.sub = G8 ? (int)(threadIdx.x & 7) : 0;
+  m.n_warp = 0; m.n_zmssd = 0; m.n_align_it = 0;
+#ifdef SVOH_SEED_STAMPS
+  m.t[0] = m.t[1] = m.t[2] = m.t[3] = 0; m.tlast = clock64();
+#endif
+  int n_ok = 0;
+  for (int j = 0; j < len; ++j) {
+    if (G8) g8_lds_fence();   // the patch of the step before has been read by every lane before this step's warp writes it
+    const DevFrameView& cur = a.cur_frame[c.chain_idx[jb + j]];
+    // (the unit's columns are read again at every step, as a single call reads them: seven doubles less to carry through the search)
+    const Vec3 f = { a.f[3 * i], a.f[3 * i + 1], a.f[3 * i + 2] };
+    int res;
+    const bool ok = update_seed_chain_step<G8>(a, m, ref, cur, a.px[2 * i], a.px[2 * i + 1], f, a.grad[2 * i], a.grad[2 * i + 1], a.level[i], st, type, res);
+    n_ok += ok ? 1 : 0;
+    if (reporter) {
+      if (c.step_result) c.step_result[(size_t)i * c.max_steps + j] = res;
+      if (c.step_success) c.step_success[(size_t)i * c.max_steps + j] = ok ? 1 : 0;
+    }
+  }
+  if (!reporter) return;
+  for (int j = len; j < c.max_steps; ++j) {   // beyond the unit's chain
+    if (c.step_result) c.step_result[(size_t)i * c.max_steps + j] = SVOH_MATCH_NOT_RUN;
+    if (c.step_success) c.step_success[(size_t)i * c.max_steps + j] = 0;
+  }
+  a.state[4 * i] = st[0]; a.state[4 * i + 1] = st[1]; a.state[4 * i + 2] = st[2]; a.state[4 * i + 3] = st[3];
+  a.type[i] = (uint8_t)type;
+  c.steps_succeeded[i] = n_ok;
+  flush_counters(a.unit_counts, i, m, n_ok);
+}
+
 // ---- spatial binning of a large seed batch -------------------------------------------------------------------------
 // Seeds arrive in the detector's order (by score): neighbours in the batch lie anywhere in the image, so every seed
 // pulls its own ~20 cache lines (10-12 rows of the reference patch, as many of the current image) through L2 and
@@ -3309,6 +3432,152 @@ static int run_epipolar(svoh_ctx* ctx, const svoh_matcher_options* mopt, int n_r
   return SVOH_OK;
 }
 
+// svoh_update_seeds_chain: [views (reference, then chain frames) | chains | inputs | state, type | outputs] through a staging
+// pair of its own (h_seed_chain / d_seed_chain): the deferred section's queued or flushed batches are not touched
+static int run_seed_chain(svoh_ctx* ctx, const svoh_matcher_options* mopt, const svoh_depth_filter_options* dopt, int n_ref_frames,
+                          const svoh_frame_view* ref_frames, const svoh_feature_batch* fb, double* state, int n_chain_frames,
+                          const svoh_frame_view* chain_frames, const int32_t* chain_begin, const int32_t* chain_idx,
+                          int32_t* n_success, int32_t* steps_succeeded, int32_t* step_result, uint8_t* step_success, int max_steps)
+{
+  if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  SVOH_REQUIRE(ctx, mopt && dopt && fb, "NULL argument");
+  const int n = fb->n;
+  if (n_success) *n_success = 0;
+  if (n <= 0) return SVOH_OK;
+  SVOH_REQUIRE(ctx, ref_frames && chain_begin && n_ref_frames >= 1 && n_chain_frames >= 0, "NULL argument");
+  SVOH_REQUIRE(ctx, fb->mem_space == SVOH_MEM_HOST, "svoh_update_seeds_chain: host arrays only (SVOH_MEM_HOST)");
+  SVOH_REQUIRE(ctx, fb->layout == SVOH_BATCH_UNITS && !fb->feature_index && !fb->cur_frame_idx,
+               "svoh_update_seeds_chain: SVOH_BATCH_UNITS without feature_index and cur_frame_idx (the chains name the current frames)");
+  SVOH_REQUIRE(ctx, fb->ref_frame_idx && fb->px && fb->f && fb->grad && fb->level && fb->type && state && steps_succeeded, "NULL feature array");
+  const bool want_steps = step_result || step_success;
+  SVOH_REQUIRE(ctx, !want_steps || max_steps >= 0, "max_steps is negative");
+  // the chains
+  SVOH_REQUIRE(ctx, chain_begin[0] == 0, "chain_begin does not start at 0");
+  int longest = 0;
+  for (int r = 0; r < n_ref_frames; ++r) {
+    SVOH_REQUIRE(ctx, chain_begin[r + 1] >= chain_begin[r], "chain_begin decreases");
+    longest = std::max(longest, chain_begin[r + 1] - chain_begin[r]);
+  }
+  const int n_links = chain_begin[n_ref_frames];
+  SVOH_REQUIRE(ctx, n_links == 0 || (chain_idx && chain_frames), "NULL chain argument");
+  for (int k = 0; k < n_links; ++k)
+    SVOH_REQUIRE(ctx, chain_idx[k] >= 0 && chain_idx[k] < n_chain_frames, "chain_idx out of range");
+  SVOH_REQUIRE(ctx, !want_steps || max_steps >= longest, "max_steps is smaller than the longest chain");
+  for (int i = 0; i < n; ++i) {
+    SVOH_REQUIRE(ctx, fb->ref_frame_idx[i] >= 0 && fb->ref_frame_idx[i] < n_ref_frames, "ref_frame_idx out of range");
+    SVOH_REQUIRE(ctx, fb->level[i] >= 0 && fb->level[i] < SVOH_MAX_LEVELS, "feature level out of range");
+  }
+  std::vector<DevFrameView> views((size_t)n_ref_frames + n_chain_frames);
+  for (int k = 0; k < n_ref_frames; ++k) {
+    const int rc = fill_view(ctx, ref_frames[k], &views[k], "reference frame");
+    if (rc != SVOH_OK) return rc;
+  }
+  for (int k = 0; k < n_chain_frames; ++k) {
+    const int rc = fill_view(ctx, chain_frames[k], &views[n_ref_frames + k], "chain frame");
+    if (rc != SVOH_OK) return rc;
+  }
+  // the search level is chosen up to the reference pyramid's top and read from the current frame (run_matcher)
+  for (int r = 0; r < n_ref_frames; ++r)
+    for (int k = chain_begin[r]; k < chain_begin[r + 1]; ++k)
+      SVOH_REQUIRE(ctx, views[n_ref_frames + chain_idx[k]].n_levels >= views[r].n_levels, "a chain frame has fewer pyramid levels than its reference frame");
+  for (int i = 0; i < n; ++i)
+    SVOH_REQUIRE(ctx, fb->level[i] < views[fb->ref_frame_idx[i]].n_levels, "feature level beyond the reference pyramid");
+  const size_t n_steps_out = want_steps ? (size_t)n * max_steps : 0;
+  if (n_links == 0) {   // nothing to walk: no launch
+    memset(steps_succeeded, 0, sizeof(int32_t) * n);
+    if (step_result) for (size_t k = 0; k < n_steps_out; ++k) step_result[k] = SVOH_MATCH_NOT_RUN;
+    if (step_success && n_steps_out) memset(step_success, 0, n_steps_out);
+    return SVOH_OK;
+  }
+  SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
+
+  Staging s;
+  const size_t o_views = s.add(views.data(), sizeof(DevFrameView) * views.size());
+  const size_t o_begin = s.add(chain_begin, sizeof(int32_t) * ((size_t)n_ref_frames + 1));
+  const size_t o_cidx = s.add(chain_idx, sizeof(int32_t) * n_links);
+  const size_t o_idx = s.add(fb->ref_frame_idx, sizeof(int32_t) * n);
+  const size_t o_px = s.add(fb->px, sizeof(double) * 2 * n);
+  const size_t o_f = s.add(fb->f, sizeof(double) * 3 * n);
+  const size_t o_grad = s.add(fb->grad, sizeof(double) * 2 * n);
+  const size_t o_level = s.add(fb->level, sizeof(int32_t) * n);
+  const size_t o_type = s.add(fb->type, (size_t)n);
+  const size_t o_state = s.add(state, sizeof(double) * 4 * n);
+  const size_t in_total = s.total;
+  auto out_add = [&](size_t bytes) { const size_t o = s.total; s.total = (s.total + bytes + 63) & ~(size_t)63; return o; };
+  const size_t o_nok = out_add(sizeof(int32_t) * n);
+  const size_t o_sres = step_result ? out_add(sizeof(int32_t) * n_steps_out) : 0;
+  const size_t o_ssucc = step_success ? out_add(n_steps_out) : 0;
+  const size_t o_end = s.total;
+  SVOH_HIP_TRY(ctx, ctx->h_seed_chain.reserve(s.total));
+  SVOH_HIP_TRY(ctx, ctx->d_seed_chain.reserve(s.total));
+  uint8_t* h = static_cast<uint8_t*>(ctx->h_seed_chain.ptr);
+  uint8_t* d = static_cast<uint8_t*>(ctx->d_seed_chain.ptr);
+  for (size_t k = 0; k < s.in.size(); ++k) memcpy(h + s.off[k], s.in[k].first, s.in[k].second);
+  SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d, h, in_total));
+
+  MatcherArgs a;
+  memset(&a, 0, sizeof a);
+  a.ref_frames = reinterpret_cast<const DevFrameView*>(d + o_views);
+  a.cur_frame = a.ref_frames + n_ref_frames;
+  a.mopt = *mopt;
+  a.dopt = *dopt;
+  a.n = n;
+  a.n_ref_frames = n_ref_frames;
+  a.n_cur_frames = n_chain_frames;
+  a.ref_frame_idx = reinterpret_cast<const int32_t*>(d + o_idx);
+  a.px = reinterpret_cast<const double*>(d + o_px);
+  a.f = reinterpret_cast<const double*>(d + o_f);
+  a.grad = reinterpret_cast<const double*>(d + o_grad);
+  a.level = reinterpret_cast<const int32_t*>(d + o_level);
+  a.type = d + o_type;
+  a.state = reinterpret_cast<double*>(d + o_state);
+  SeedChainArgs c;
+  c.chain_begin = reinterpret_cast<const int32_t*>(d + o_begin);
+  c.chain_idx = reinterpret_cast<const int32_t*>(d + o_cidx);
+  c.steps_succeeded = reinterpret_cast<int32_t*>(d + o_nok);
+  c.step_result = step_result ? reinterpret_cast<int32_t*>(d + o_sres) : nullptr;
+  c.step_success = step_success ? d + o_ssucc : nullptr;
+  c.max_steps = want_steps ? max_steps : 0;
+  // the geometries of a small seed batch: eight lanes per unit unless the knob asks for one lane (0) or one wave (3);
+  // there is no packed form (2: eight lanes)
+  int g8 = SvohKnobs::or_default(ctx->knobs.matcher_g8, 1);
+  if (g8 != 0 && g8 != 3) g8 = 1;
+  const int units_per_block = g8 == 1 ? 8 : (g8 == 3 ? 1 : 64);
+  const dim3 grid((unsigned)((n + units_per_block - 1) / units_per_block)), block(64);
+  {
+    unsigned long long* dummy;
+    int rc = reset_counters(ctx, &dummy);
+    if (rc == SVOH_OK) rc = reserve_unit_counts(ctx, (size_t)n, &a.unit_counts);
+    if (rc != SVOH_OK) return rc;
+  }
+  if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_start, ctx->stream));
+  if (g8 == 3) hipLaunchKernelGGL(update_seeds_chain_kernel<3>, grid, block, 0, ctx->stream, a, c);
+  else if (g8) hipLaunchKernelGGL(update_seeds_chain_kernel<1>, grid, block, 0, ctx->stream, a, c);
+  else hipLaunchKernelGGL(update_seeds_chain_kernel<0>, grid, block, 0, ctx->stream, a, c);
+  SVOH_HIP_TRY(ctx, hipGetLastError());
+  if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_stop, ctx->stream));
+  ctx->misc_timed = ctx->timing_on(); ctx->misc_launched = true;
+  {
+    const int rc = reduce_unit_counts(ctx, (size_t)n);
+    if (rc != SVOH_OK) return rc;
+  }
+  // type, state and the outputs lie behind one another: one copy back
+  SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, h + o_type, d + o_type, o_end - o_type));
+  SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(fb->type, h + o_type, (size_t)n);
+  memcpy(state, h + o_state, sizeof(double) * 4 * n);
+  memcpy(steps_succeeded, h + o_nok, sizeof(int32_t) * n);
+  if (step_result) memcpy(step_result, h + o_sres, sizeof(int32_t) * n_steps_out);
+  if (step_success && n_steps_out) memcpy(step_success, h + o_ssucc, n_steps_out);
+  if (n_success) {
+    int32_t total = 0;
+    for (int i = 0; i < n; ++i) total += steps_succeeded[i];
+    *n_success = total;
+  }
+  return SVOH_OK;
+}
+
 
 // ---- f-4: candidate projection of Reprojector::reprojectFrames ---------------------------------------------------
 // reprojector_utils::getCandidate / projectPointAndCheckVisibility (src/svo/src/reprojector.cpp:489-543) with
@@ -4385,6 +4654,16 @@ int svoh_update_seeds_batch(svoh_ctx* ctx, const svoh_matcher_options* matcher_o
 try {
   return run_matcher(ctx, true, matcher_options, options, n_ref_frames, ref_frames, cur_frame, features, nullptr, nullptr,
                      match_result, nullptr, nullptr, nullptr, nullptr, state, success, n_success);
+} SVOH_ABI_CATCH(ctx)
+
+int svoh_update_seeds_chain(svoh_ctx* ctx, const svoh_matcher_options* matcher_options, const svoh_depth_filter_options* options,
+                            int n_ref_frames, const svoh_frame_view* ref_frames, const svoh_feature_batch* features, double* state,
+                            int n_chain_frames, const svoh_frame_view* chain_frames, const int32_t* chain_begin,
+                            const int32_t* chain_idx, int32_t* n_success, int32_t* steps_succeeded, int32_t* step_result,
+                            uint8_t* step_success, int max_steps)
+try {
+  return run_seed_chain(ctx, matcher_options, options, n_ref_frames, ref_frames, features, state, n_chain_frames, chain_frames,
+                        chain_begin, chain_idx, n_success, steps_succeeded, step_result, step_success, max_steps);
 } SVOH_ABI_CATCH(ctx)
 
 int svoh_update_seeds_batch_ex(svoh_ctx* ctx, const svoh_matcher_options* matcher_options,

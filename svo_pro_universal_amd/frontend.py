@@ -404,6 +404,33 @@ def _update_seeds_batch(self, mopt, dopt, ref_views, cur_view, fb, state):
     return ns.value, st, success[:n], mr[:n]
 
 
+def _update_seeds_chain(self, mopt, dopt, ref_views, fb, state, chain_views, chains, want_steps=True, max_steps=None):
+    """svoh_update_seeds_chain: the seeds of ref_views[r] walk chain_views[k] for k in chains[r], state and type carried on
+    the device (fb's type array is updated in place).  Returns (n_success, state, steps_succeeded, step_result, step_success);
+    the last two are n x max_steps (None without want_steps; max_steps defaults to the longest chain)."""
+    n = fb.n
+    assert len(chains) == len(ref_views)
+    rv = (capi.svoh_frame_view * max(len(ref_views), 1))(*ref_views)
+    cv = (capi.svoh_frame_view * max(len(chain_views), 1))(*chain_views)
+    begin = np.zeros(len(chains) + 1, np.int32)
+    begin[1:] = np.cumsum([len(c) for c in chains])
+    idx = np.ascontiguousarray([k for c in chains for k in c] or [0], np.int32)
+    if max_steps is None:
+        max_steps = max([len(c) for c in chains] or [0])
+    st = np.ascontiguousarray(state, np.float64).copy()
+    n_ok = np.zeros(max(n, 1), np.int32)
+    res = np.zeros((max(n, 1), max(max_steps, 1)), np.int32) if want_steps else None
+    suc = np.zeros((max(n, 1), max(max_steps, 1)), np.uint8) if want_steps else None
+    ns = C.c_int32()
+    self._check(self.lib.svoh_update_seeds_chain(self.h, C.byref(mopt), C.byref(dopt), len(ref_views), rv, C.byref(fb),
+                                                 st.ctypes.data, len(chain_views), cv, begin.ctypes.data, idx.ctypes.data,
+                                                 C.byref(ns), n_ok.ctypes.data, res.ctypes.data if want_steps else None,
+                                                 suc.ctypes.data if want_steps else None, int(max_steps)))
+    if want_steps:
+        res, suc = res[:n, :max_steps], suc[:n, :max_steps]
+    return ns.value, st, n_ok[:n], res, suc
+
+
 def make_feature_batch_device(n, ref_frame_idx, px, f, grad, level, ftype, cur_frame_idx=0, n_cur_frames=0):
     """Feature batch whose arrays are DEVICE pointers (ints, e.g. torch.Tensor.data_ptr()); the caller keeps
     the owning tensors alive until the stream has run the call."""
@@ -629,3 +656,4 @@ Context.update_seeds_device = _update_seeds_device
 Context.match_direct_device = _match_direct_device
 Context.match_direct_batch = _match_direct_batch
 Context.update_seeds_batch = _update_seeds_batch
+Context.update_seeds_chain = _update_seeds_chain

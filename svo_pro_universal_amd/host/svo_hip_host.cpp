@@ -274,6 +274,39 @@ size_t DepthFilterHip::updateSeeds(const std::vector<FramePtr>& ref_frames_with_
   return finishUpdateSeeds();
 }
 
+size_t DepthFilterHip::updateSeedsWithFrames(const FramePtr& keyframe, const std::vector<FramePtr>& frames)
+{
+  if (!keyframe) throw std::runtime_error("DepthFilterHip::updateSeedsWithFrames: NULL keyframe");
+  for (const FramePtr& f : frames) if (!f) throw std::runtime_error("DepthFilterHip::updateSeedsWithFrames: NULL frame");
+  if (async_open_)   // (the update in flight copied its keyframes' seeds when it was queued; this keyframe's would be overwritten when it is written back)
+    for (const FramePtr& f : pending_.frames) if (f == keyframe) throw std::runtime_error("DepthFilterHip::updateSeedsWithFrames: the keyframe is part of the update in flight");
+  const size_t n = keyframe->num_features_;
+  if (n == 0 || frames.empty()) return 0;   // (last_results_ is left alone: the update in flight writes into it when it is collected)
+  Frame& r = *keyframe;
+  const svoh_frame_view ref = view_of(r);
+  std::vector<svoh_frame_view> chain;
+  std::vector<int32_t> chain_idx;
+  for (const FramePtr& f : frames) { chain_idx.push_back(static_cast<int32_t>(chain.size())); chain.push_back(view_of(*f)); }
+  const int32_t chain_begin[2] = { 0, static_cast<int32_t>(frames.size()) };
+  const std::vector<int32_t> ref_idx(n, 0);
+  std::vector<uint8_t> type(r.type_vec_.begin(), r.type_vec_.begin() + n);
+  std::vector<double> state(r.invmu_sigma2_a_b_vec_.begin(), r.invmu_sigma2_a_b_vec_.begin() + 4 * n);
+  std::vector<int32_t> steps_succeeded(n, 0);
+  svoh_feature_batch fb{};
+  fb.n = static_cast<int32_t>(n);
+  fb.ref_frame_idx = ref_idx.data(); fb.px = r.px_vec_.data(); fb.f = r.f_vec_.data(); fb.grad = r.grad_vec_.data();
+  fb.level = r.level_vec_.data(); fb.type = type.data();
+  const svoh_depth_filter_options o = abiOptions(*frames.front());   // (px_error_angle is the process-wide one whichever frame is asked)
+  int32_t n_success = 0;
+  if (svoh_update_seeds_chain(ctx_, &matcher_options_, &o, 1, &ref, &fb, state.data(), static_cast<int>(chain.size()), chain.data(), chain_begin,
+                              chain_idx.data(), &n_success, steps_succeeded.data(), nullptr, nullptr, 0) != SVOH_OK)
+    throw std::runtime_error(std::string("svoh_update_seeds_chain: ") + svoh_last_error_string(ctx_));
+  // (units that are no seeds come back as they went)
+  std::copy(state.begin(), state.end(), r.invmu_sigma2_a_b_vec_.begin());
+  std::copy(type.begin(), type.end(), r.type_vec_.begin());
+  return static_cast<size_t>(n_success);
+}
+
 void DepthFilterHip::updateSeedsAsync(const std::vector<FramePtr>& ref_frames_with_seeds, const FramePtr& cur_frame)
 {
   if (prepared_) {

@@ -265,6 +265,13 @@ class DepthFilterHip {
   // returns the number of successfully updated seeds; updates invmu_sigma2_a_b_vec_ and
   // type_vec_ of the reference frames in place, exactly like the reference
   size_t updateSeeds(const std::vector<FramePtr>& ref_frames_with_seeds, const FramePtr& cur_frame);
+  // FrameHandlerMono::processFrame with update_seeds_with_old_keyframes (frame_handler_mono.cpp:218-225): the seeds of a NEW
+  // keyframe against `frames` in turn -- the equivalent of `for f in frames: updateSeeds({keyframe}, f)`, in ONE device call
+  // (svoh_update_seeds_chain: every seed walks the list on the device, state and type carried from frame to frame).  States
+  // and types are written back to the keyframe's columns; returns the successes summed over all frames.  Blocking.  Usable
+  // while updateSeedsAsync of OTHER keyframes is in flight (it stages through buffers of its own and leaves the deferred
+  // section alone); lastMatchResults() is not touched.
+  size_t updateSeedsWithFrames(const FramePtr& keyframe, const std::vector<FramePtr>& frames);
   // The same in two halves: updateSeedsAsync sends the update to the device and returns (the reference frames must
   // not be touched by anything that reads or writes their seeds until the update is finished -- appending features to
   // them is fine); finishUpdateSeeds waits for it, writes the states and types back and returns the success count.

@@ -366,6 +366,7 @@ FrontendParams frontendParamsFromYaml(const YamlNode& node)
   p.depth_filter.mappoint_convergence_sigma2_thresh = node["mappoint_convergence_sigma2_thresh"].asDouble(500.0);
   p.depth_filter.scan_epi_unit_sphere = node["scan_epi_unit_sphere"].asBool(false);
   p.poseoptim_using_unit_sphere = node["poseoptim_using_unit_sphere"].asBool(false);
+  p.update_seeds_with_old_keyframes = node["update_seeds_with_old_keyframes"].asBool(true);
   p.depth_filter.affine_est_offset = node["depth_filter_affine_est_offset"].asBool(true);
   p.depth_filter.affine_est_gain = node["depth_filter_affine_est_gain"].asBool(false);
   p.max_n_seeds_per_frame = (int)((double)node["max_fts"].asInt(120) * node["max_seeds_ratio"].asDouble(3.0));

@@ -80,6 +80,10 @@ struct FrontendParams {
   int n_pyr_levels_to_build = 5;             // img_align_max_level + 1 (frame_handler_base.cpp:186)
   int structure_optimization_max_pts = 20;   // structure_optimization_max_pts (svo_factory.cpp:122)
   bool poseoptim_using_unit_sphere = false;  // pose optimiser on bearing-vector differences (frame_handler_base.cpp:137-138)
+  // update_seeds_with_old_keyframes (svo_factory.cpp:147-148, default true): a new keyframe's seeds are updated with the last
+  // frame and the overlap keyframes (frame_handler_mono.cpp:218-225).  Parsed only: the chains act on it where they are asked to
+  // (svoh_mini_frontend: SVOH_MINI_SEEDS_OLD_KEYFRAMES; LockstepOptions::seeds_old_keyframes)
+  bool update_seeds_with_old_keyframes = true;
 };
 FrontendParams frontendParamsFromYaml(const YamlNode& node);
 FrontendParams loadFrontendParams(const std::string& param_yaml_path);

@@ -78,6 +78,11 @@ struct FrontendLockstep::Stream {
   CameraMaskPtr mask;            // the stream's camera mask, or null ...
   svoh_mask_t mask_handle = 0;   // ... and its copy on the device (shared by the streams with the same image)
   std::vector<FrontendLockstep::NewFeature> new_features;
+  // seeds_old_keyframes: the frames the new keyframe's seeds walk (last frame, then the overlap keyframes; held until the call has run),
+  // the keyframe's feature count before its new seeds, where its units lie in the round's call, and the rows of seed_chain.csv
+  std::vector<FramePtr> chain_frames;
+  size_t chain_n_old = 0, chain_off = 0;
+  std::vector<FrontendLockstep::SeedChainRow> seed_chain_rows;
   int detect_max_n = 0;
   // the depth-filter update in flight
   std::vector<FramePtr> seed_frames;
@@ -229,6 +234,13 @@ const Transformation& FrontendLockstep::pose(int s) const
 }
 
 size_t FrontendLockstep::keyframesAlive(int s) const { return streams_.at(static_cast<size_t>(s))->kfs.size(); }
+
+std::vector<FrontendLockstep::SeedChainRow> FrontendLockstep::seedChainRows(int s)
+{
+  std::vector<SeedChainRow> out;
+  out.swap(streams_.at(static_cast<size_t>(s))->seed_chain_rows);
+  return out;
+}
 
 std::vector<FrontendLockstep::FrameRow> FrontendLockstep::completedRows(int s)
 {
@@ -420,6 +432,14 @@ void FrontendLockstep::makeKeyframes(const std::vector<int>& which)
     // bootstrap stand-in for the initialiser's landmarks: a keyframe's own new seeds are usable for the
     // alignment of the next frame at their current depth estimate (self reference)
     for (size_t i = n_old; i < f->num_features_; ++i) { f->seed_ref_vec_[i].keyframe = f; f->seed_ref_vec_[i].seed_id = static_cast<int>(i); }
+    // (seeds_old_keyframes: the list the new seeds walk, as the single-stream harness makes it -- the last frame, then the keyframes
+    // this frame was reprojected from; a stream's first keyframe has no last frame and no step)
+    st.chain_frames.clear();
+    st.chain_n_old = n_old;
+    if (opt_.seeds_old_keyframes && st.so.params.update_seeds_with_old_keyframes && st.tracking && st.last) {
+      st.chain_frames.push_back(st.last);
+      st.chain_frames.insert(st.chain_frames.end(), st.kfs.begin(), st.kfs.end());
+    }
     st.kfs.push_back(f);
     while (st.kfs.size() > st.reprojector.options_.max_n_kfs) {
       for (auto& sr : st.kfs.front()->seed_ref_vec_) sr.keyframe.reset();   // break the self references
@@ -428,6 +448,7 @@ void FrontendLockstep::makeKeyframes(const std::vector<int>& which)
     }
   });
   detect_ = DetectBatch();
+  if (opt_.seeds_old_keyframes) updateNewKeyframeSeeds(which);
   // the new keyframes' features are final now: their constant columns go to the device once, in one call
   if (opt_.resident_features) {
     const size_t m = which.size();
@@ -444,6 +465,64 @@ void FrontendLockstep::makeKeyframes(const std::vector<int>& which)
     ++device_calls_;
     for (size_t w = 0; w < m; ++w) streams_[static_cast<size_t>(which[w])]->frame->features = handles[w];
   }
+}
+
+// frame_handler_mono.cpp:218-225 for every stream that made a keyframe in this round: ONE svoh_update_seeds_chain call -- a reference
+// view per stream (its new keyframe), its chain of frames (the last frame, then its overlap keyframes), the frames of all streams in one
+// list.  Every stream's slice is what DepthFilterHip::updateSeedsWithFrames computes for it alone (units do not interact, the options
+// are shared by the streams of an engine).  The depth-filter update of the round is in flight meanwhile: it names other keyframes, and
+// the call stages through buffers of its own.
+void FrontendLockstep::updateNewKeyframeSeeds(const std::vector<int>& which)
+{
+  std::vector<int> who;
+  for (int s : which) if (!streams_[static_cast<size_t>(s)]->chain_frames.empty()) who.push_back(s);
+  if (!who.empty()) {
+    std::vector<svoh_frame_view> refs, chain;
+    std::vector<int32_t> chain_begin(1, 0), chain_idx, ref_idx, level;
+    std::vector<double> px, f, grad, state;
+    std::vector<uint8_t> type;
+    for (size_t w = 0; w < who.size(); ++w) {
+      Stream& st = *streams_[static_cast<size_t>(who[w])];
+      const Frame& r = *st.frame;
+      const size_t n = r.num_features_;
+      st.chain_off = ref_idx.size();
+      refs.push_back(detail::viewOf(r));
+      for (const FramePtr& c : st.chain_frames) { chain_idx.push_back(static_cast<int32_t>(chain.size())); chain.push_back(detail::viewOf(*c)); }
+      chain_begin.push_back(static_cast<int32_t>(chain_idx.size()));
+      ref_idx.insert(ref_idx.end(), n, static_cast<int32_t>(w));
+      px.insert(px.end(), r.px_vec_.begin(), r.px_vec_.begin() + 2 * n); f.insert(f.end(), r.f_vec_.begin(), r.f_vec_.begin() + 3 * n);
+      grad.insert(grad.end(), r.grad_vec_.begin(), r.grad_vec_.begin() + 2 * n); level.insert(level.end(), r.level_vec_.begin(), r.level_vec_.begin() + n);
+      type.insert(type.end(), r.type_vec_.begin(), r.type_vec_.begin() + n);
+      state.insert(state.end(), r.invmu_sigma2_a_b_vec_.begin(), r.invmu_sigma2_a_b_vec_.begin() + 4 * n);
+    }
+    DepthFilterHip df(ctx_, opt_.params.depth_filter);   // (options only)
+    const svoh_depth_filter_options dfo = df.abiOptions(*streams_[static_cast<size_t>(who[0])]->chain_frames.front());
+    const svoh_matcher_options df_mopt = df.getMatcherOptions();
+    svoh_feature_batch fb{};
+    fb.n = static_cast<int32_t>(ref_idx.size());
+    fb.ref_frame_idx = ref_idx.data(); fb.px = px.data(); fb.f = f.data(); fb.grad = grad.data(); fb.level = level.data(); fb.type = type.data();
+    std::vector<int32_t> steps_succeeded(ref_idx.size(), 0);
+    check(svoh_update_seeds_chain(ctx_, &df_mopt, &dfo, static_cast<int>(refs.size()), refs.data(), &fb, state.data(), static_cast<int>(chain.size()), chain.data(),
+                                  chain_begin.data(), chain_idx.data(), nullptr, steps_succeeded.data(), nullptr, nullptr, 0), "svoh_update_seeds_chain");
+    ++device_calls_;
+    pool_.run(static_cast<int>(who.size()), [&](int w) {
+      Stream& st = *streams_[static_cast<size_t>(who[static_cast<size_t>(w)])];
+      Frame& r = *st.frame;
+      const size_t n = r.num_features_, off = st.chain_off;
+      std::copy(state.begin() + 4 * off, state.begin() + 4 * (off + n), r.invmu_sigma2_a_b_vec_.begin());
+      std::copy(type.begin() + off, type.begin() + off + n, r.type_vec_.begin());
+      SeedChainRow row;
+      row.k = static_cast<size_t>(r.id_); row.n_chain_frames = st.chain_frames.size(); row.n_seeds = n - st.chain_n_old;
+      for (size_t i = 0; i < n; ++i) row.n_step_successes += static_cast<size_t>(steps_succeeded[off + i]);
+      for (size_t i = st.chain_n_old; i < n; ++i) {
+        const int t = r.type_vec_[i];
+        row.n_converged_after += t == SVOH_FT_CORNER_SEED_CONVERGED || t == SVOH_FT_EDGELET_SEED_CONVERGED || t == SVOH_FT_MAPPOINT_SEED_CONVERGED;
+      }
+      st.seed_chain_rows.push_back(row);
+    });
+  }
+  // (the popped keyframes' pyramids were held by the lists until here)
+  for (int s : which) streams_[static_cast<size_t>(s)]->chain_frames.clear();
 }
 
 void FrontendLockstep::prefetch(const uint8_t* const* next_images, int pitch)
@@ -1051,6 +1130,7 @@ void FrontendLockstep::addImages(const uint8_t* const* images, int pitch, const 
 struct svohl_engine {
   std::unique_ptr<svo_hip::FrontendLockstep> fe;
   std::vector<std::vector<svo_hip::FrontendLockstep::FrameRow>> backlog;   // rows taken from the engine and not handed out yet
+  std::vector<std::deque<svo_hip::FrontendLockstep::SeedChainRow>> seed_chain_backlog;
 };
 
 namespace {
@@ -1127,6 +1207,7 @@ static int svohl_create_impl(svoh_ctx* ctx, int n_streams, const svoh_camera* ca
     std::unique_ptr<svohl_engine> e(new svohl_engine);
     e->fe.reset(new svo_hip::FrontendLockstep(ctx, n_streams, lo));
     e->backlog.resize(static_cast<size_t>(n_streams));
+    e->seed_chain_backlog.resize(static_cast<size_t>(n_streams));
     *out = e.release();
   });
 }
@@ -1171,6 +1252,7 @@ static int svohl_create_streams_impl(svoh_ctx* ctx, int n_streams, const svoh_ca
     std::unique_ptr<svohl_engine> e(new svohl_engine);
     e->fe.reset(new svo_hip::FrontendLockstep(ctx, n_streams, lo));
     e->backlog.resize(static_cast<size_t>(n_streams));
+    e->seed_chain_backlog.resize(static_cast<size_t>(n_streams));
     *out = e.release();
   });
 }
@@ -1257,6 +1339,33 @@ int svohl_set_stream_mask(svohl_engine* e, int stream, int width, int height, in
   return svohl_guard([&] {
     if (!e) throw std::runtime_error("svohl_set_stream_mask: NULL engine");
     e->fe->setStreamMask(stream, width, height, pitch, data);
+  });
+}
+
+int svohl_set_seeds_old_keyframes(svohl_engine* e, int on)
+{
+  return svohl_guard([&] {
+    if (!e) throw std::runtime_error("svohl_set_seeds_old_keyframes: NULL engine");
+    e->fe->setSeedsOldKeyframes(on != 0);
+  });
+}
+
+int svohl_seed_chain_rows(svohl_engine* e, int stream, int max_rows, int64_t* rows, int* n_rows)
+{
+  return svohl_guard([&] {
+    if (!e || !n_rows || (max_rows > 0 && !rows) || stream < 0 || stream >= e->fe->numStreams()) throw std::runtime_error("svohl_seed_chain_rows: bad argument");
+    auto& b = e->seed_chain_backlog.at(static_cast<size_t>(stream));
+    for (const auto& r : e->fe->seedChainRows(stream)) b.push_back(r);
+    int n = 0;
+    while (n < max_rows && !b.empty()) {
+      const auto& r = b.front();
+      int64_t* o = rows + 5 * n;
+      o[0] = static_cast<int64_t>(r.k); o[1] = static_cast<int64_t>(r.n_chain_frames); o[2] = static_cast<int64_t>(r.n_seeds);
+      o[3] = static_cast<int64_t>(r.n_step_successes); o[4] = static_cast<int64_t>(r.n_converged_after);
+      b.pop_front();
+      ++n;
+    }
+    *n_rows = n;
   });
 }
 

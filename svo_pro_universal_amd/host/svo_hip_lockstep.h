@@ -94,6 +94,11 @@ struct LockstepOptions {
   // through the structure optimisation (frame_handler_mono.cpp:157) -- all streams' points in ONE svoh_optimize_points_batch per round.
   // false: the seed-only chain of round 5.
   bool landmarks = true;
+  // FrameHandlerMono::processFrame with update_seeds_with_old_keyframes (frame_handler_mono.cpp:218-225): the seeds of a stream's new
+  // keyframe are updated with its last frame and its overlap keyframes -- ONE svoh_update_seeds_chain call per round for all
+  // streams that made a keyframe (a reference view per stream, ragged chains), before the new keyframes' columns go resident.  Acts on the
+  // streams whose parameter file does not switch the key off.  false (default): the chain as it was.
+  bool seeds_old_keyframes = false;
   // one entry per stream, or empty: every stream runs with params / depth_* / kf_every / min_tracked above
   std::vector<LockstepStreamOptions> per_stream;
 };
@@ -129,6 +134,11 @@ class FrontendLockstep {
   // a stream's mask given after construction and before the stream's first frame (the C face: svohl_set_stream_mask); copies the image
   void setStreamMask(int s, int width, int height, int pitch, const uint8_t* data);
   size_t masksOnDevice() const { return masks_.size(); }
+  // LockstepOptions::seeds_old_keyframes given after construction, before the first round (the C face: svohl_set_seeds_old_keyframes)
+  void setSeedsOldKeyframes(bool on) { opt_.seeds_old_keyframes = on; }
+  // with seeds_old_keyframes: what the step did at stream s' keyframes since the last call (the columns of svoh_mini_frontend's seed_chain.csv)
+  struct SeedChainRow { size_t k = 0, n_chain_frames = 0, n_seeds = 0, n_step_successes = 0, n_converged_after = 0; };
+  std::vector<SeedChainRow> seedChainRows(int s);
   const RoundTimes& lastRoundTimes() const { return times_; }
   size_t keyframesAlive(int s) const;
   // waits for the depth-filter update in flight and completes the last rows
@@ -152,6 +162,7 @@ class FrontendLockstep {
   svoh_mask_t maskHandleFor(const CameraMaskPtr& m);
   void startDetection(const std::vector<int>& which);
   void makeKeyframes(const std::vector<int>& which);
+  void updateNewKeyframeSeeds(const std::vector<int>& which);   // seeds_old_keyframes: the round's ONE chain call
   // the detector batch of the round's new keyframes between its two halves
   struct DetectBatch {
     std::vector<int> started_for, streams;   // the streams it was started for; those among them whose frame has room for seeds (slot order)

@@ -65,6 +65,13 @@ int svohl_run_schedule(svohl_engine* e, const uint8_t* base, size_t image_bytes,
  * distinct mask on the device (streams given equal masks share it), released with the engine; the keyframes' detector takes it. */
 int svohl_set_stream_mask(svohl_engine* e, int stream, int width, int height, int pitch, const uint8_t* data);
 int svohl_masks_on_device(svohl_engine* e, int* n_masks);
+/* LockstepOptions::seeds_old_keyframes, given after the engine is made and before its first round (off when the engine is made): a new
+ * keyframe's seeds are updated with the stream's last frame and its overlap keyframes (update_seeds_with_old_keyframes of the reference's
+ * frame handler), one svoh_update_seeds_chain call per round for all streams that made a keyframe. */
+int svohl_set_seeds_old_keyframes(svohl_engine* e, int on);
+/* what that step did at the keyframes of `stream` since the last call: 5 integers each (frame, n_chain_frames, n_seeds, n_step_successes,
+ * n_converged_after); at most max_rows are handed out, *n_rows = how many */
+int svohl_seed_chain_rows(svohl_engine* e, int stream, int max_rows, int64_t* rows, int* n_rows);
 int svohl_pose(svohl_engine* e, int stream, svoh_se3* T_f_w);
 /* pyramid, align, reproject, pose, seeds, keyframe, total of the last round (ms) and its device calls */
 int svohl_last_round(svohl_engine* e, double times_ms[7], int* device_calls);

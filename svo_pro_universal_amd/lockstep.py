@@ -41,6 +41,8 @@ def load_host():
     lib.svohl_pose.argtypes = [C.c_void_p, C.c_int, P(capi.svoh_se3)]
     lib.svohl_set_stream_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.svohl_masks_on_device.argtypes = [C.c_void_p, P(C.c_int)]
+    lib.svohl_set_seeds_old_keyframes.argtypes = [C.c_void_p, C.c_int]
+    lib.svohl_seed_chain_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, P(C.c_int64), P(C.c_int)]
     lib.svohs_set_stream_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.svohl_run_sequence.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p, C.c_void_p]
     lib.svohl_last_round.argtypes = [C.c_void_p, P(C.c_double), P(C.c_int)]
@@ -115,8 +117,10 @@ class Lockstep(object):
     then has no threads of its own; seed = its first stream's index among all groups)."""
 
     def __init__(self, ctx, n_streams, cam, T_B_C7, params_yaml, depth_min, depth_mean, depth_max, kf_every=8, n_workers=1, images_pinned=True,
-                 pool=None, seed=0, per_stream=None, mask=None):
-        """mask: the camera's mask (HxW uint8 of the camera's size, 0 = never a feature here) or None; a per_stream dict may carry its own under
+                 pool=None, seed=0, per_stream=None, mask=None, seeds_old_keyframes=False):
+        """seeds_old_keyframes: a new keyframe's seeds are updated with the stream's last frame and its overlap keyframes, one device call per
+        round for all streams (LockstepOptions::seeds_old_keyframes; off by default).
+        mask: the camera's mask (HxW uint8 of the camera's size, 0 = never a feature here) or None; a per_stream dict may carry its own under
         "mask" (a stream with its own "cam" takes only its own).  The engine keeps one copy per distinct mask on the device (masks_on_device).
         per_stream (round 6): a list of n_streams dicts(params_yaml, kf_every, min_tracked, depth=(min, mean, max)) -- streams that
         differ (svohl_create_streams); missing keys take the common arguments.  If any dict has "cam" (and optionally "T_B_C7"), every stream
@@ -156,6 +160,19 @@ class Lockstep(object):
             m = d["mask"] if "mask" in d else (None if "cam" in d else mask)
             if m is not None:
                 self.set_stream_mask(s, m)
+        if seeds_old_keyframes:
+            self.set_seeds_old_keyframes(True)
+
+    def set_seeds_old_keyframes(self, on):
+        """svohl_set_seeds_old_keyframes: before the first round."""
+        self._check(self.lib.svohl_set_seeds_old_keyframes(self.h, 1 if on else 0))
+
+    def seed_chain_rows(self, s, max_rows=4096):
+        """(frame, n_chain_frames, n_seeds, n_step_successes, n_converged_after) of stream s' keyframes since the last call."""
+        rows = (C.c_int64 * (5 * max_rows))()
+        n = C.c_int()
+        self._check(self.lib.svohl_seed_chain_rows(self.h, int(s), max_rows, rows, C.byref(n)))
+        return np.array(rows[:5 * n.value], dtype=np.int64).reshape(-1, 5)
 
     def set_stream_mask(self, s, mask):
         """svohl_set_stream_mask: before the stream's first frame."""

@@ -25,6 +25,12 @@
 // and comes back with the alignment's round trip, and (b) the depth filter's seed update is sent off without a wait
 // and finished at the start of the next frame, before anything reads the seeds again.  Both flows give the same
 // trajectory file byte for byte (tests/test_mini_frontend_gpu.py).
+// SVOH_MINI_SEEDS_OLD_KEYFRAMES=1 (and update_seeds_with_old_keyframes not false in the parameter file): the frame handler's step
+// at a new keyframe (frame_handler_mono.cpp:218-225) -- the fresh seeds are updated with the last frame and then with every
+// overlap keyframe, in ONE device call (DepthFilterHip::updateSeedsWithFrames); `seq` does the same with one updateSeeds call per
+// frame (the comparison arm: same bytes).  Writes <out>/seed_chain.csv (frame, n_chain_frames, n_seeds, n_step_successes,
+// n_converged_after).  Unset: the tool behaves and prints exactly as without the switch.  The lock-step mode takes the same
+// switch (LockstepOptions::seeds_old_keyframes: one call per round for all streams that made a keyframe).
 // n_streams > 1 (independent camera streams need no exchange): that many host threads, each
 // with its own svoh_ctx (own HIP stream) and its own copy of the chain's state, run the same sequence side by side on
 // ONE GPU; stream k > 0 writes into <out>/stream<k>/.  At EuRoC sizes a stream keeps the GPU busy for a small part
@@ -182,7 +188,19 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
     FramePtr last;
     const bool landmarks_on = getenv("SVOH_MINI_LANDMARKS") == nullptr || atoi(getenv("SVOH_MINI_LANDMARKS")) != 0;
     int next_point_id = 0;
-    auto make_keyframe = [&](const FramePtr& f) {
+    // the new keyframe's seeds against the last frame and the overlap keyframes: 0 off, 1 one chain call, 2 one call per frame
+    int seeds_old_kfs = 0;
+    if (const char* e = getenv("SVOH_MINI_SEEDS_OLD_KEYFRAMES")) seeds_old_kfs = std::string(e) == "1" ? 1 : std::string(e) == "seq" ? 2 : 0;
+    if (!params.update_seeds_with_old_keyframes) seeds_old_kfs = 0;
+    FILE* fsc = nullptr;
+    if (seeds_old_kfs) {
+      fsc = fopen((out_dir + "/seed_chain.csv").c_str(), "w");
+      if (!fsc) throw std::runtime_error("cannot write into " + out_dir);
+      fprintf(fsc, "frame,n_chain_frames,n_seeds,n_step_successes,n_converged_after\n");
+    }
+    std::unique_ptr<DepthFilterHip> depth_filter_seq;   // the comparison arm's calls (the chain's own filter may have an update in flight)
+    if (seeds_old_kfs == 2) depth_filter_seq.reset(new DepthFilterHip(ctx, params.depth_filter));
+    auto make_keyframe = [&](const FramePtr& f, const FramePtr& last_frame) {
       // the frame handler's step at a new keyframe (frame_handler_mono.cpp:186): the seeds this frame's features hang on become
       // landmarks (the seed update in flight, if any, leaves such a seed alone when it is written back: DepthFilterHip)
       if (landmarks_on) upgradeSeedsToFeatures(ctx, f, &next_point_id);
@@ -194,6 +212,25 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
       // alignment of the next frame at their current depth estimate (self reference)
       for (size_t i = n_old; i < f->num_features_; ++i) { f->seed_ref_vec_[i].keyframe = f; f->seed_ref_vec_[i].seed_id = (int)i; }
       if (fk) for (size_t i = n_old; i < f->num_features_; ++i) fprintf(fk, "%d,%.17g,%.17g,%d\n", f->id_, f->px_vec_[2 * i], f->px_vec_[2 * i + 1], (int)f->type_vec_[i]);
+      if (seeds_old_kfs && last_frame) {
+        // frame_handler_mono.cpp:218-225: updateSeeds({new keyframe}, last frame), then the same with every overlap keyframe in the
+        // reprojector's order (the keyframes this frame was reprojected from: `kfs` before the new one joins them)
+        std::vector<FramePtr> chain;
+        chain.push_back(last_frame);
+        chain.insert(chain.end(), kfs.begin(), kfs.end());
+        size_t n_ok = 0;
+        if (seeds_old_kfs == 1) n_ok = depth_filter.updateSeedsWithFrames(f, chain);
+        else {
+          finishPendingSeedUpdate(ctx);   // (updateSeeds needs the context's deferred section; what is written back is what the next frame's start would write)
+          for (const FramePtr& c : chain) n_ok += depth_filter_seq->updateSeeds({ f }, c);
+        }
+        size_t n_conv = 0;   // of the fresh seeds
+        for (size_t i = n_old; i < f->num_features_; ++i) {
+          const int t = f->type_vec_[i];
+          n_conv += t == SVOH_FT_CORNER_SEED_CONVERGED || t == SVOH_FT_EDGELET_SEED_CONVERGED || t == SVOH_FT_MAPPOINT_SEED_CONVERGED;
+        }
+        fprintf(fsc, "%d,%zu,%zu,%zu,%zu\n", f->id_, chain.size(), f->num_features_ - n_old, n_ok, n_conv);
+      }
       kfs.push_back(f);
       while (kfs.size() > ropt.max_n_kfs) {
         for (auto& sr : kfs.front()->seed_ref_vec_) sr.keyframe.reset();   // break the self references
@@ -265,7 +302,7 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
       bool is_kf = false;
       if (k == 0) {
         frame->T_f_w_ = T0;
-        make_keyframe(frame);
+        make_keyframe(frame, nullptr);   // (no last frame: no step)
         is_kf = true;
         t2 = t3 = t4 = t5 = now_ms();
       } else {
@@ -323,7 +360,7 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
         if (!sync_flow) depth_filter.updateSeedsAsync(visible, frame);
         t5 = now_ms();
         // 5. keyframe rule
-        if (k % kf_every == 0 || frame->numTrackedFeatures() < min_tracked) { make_keyframe(frame); is_kf = true; }
+        if (k % kf_every == 0 || frame->numTrackedFeatures() < min_tracked) { make_keyframe(frame, last); is_kf = true; }
         if (sync_flow) { depth_filter.updateSeedsAsync(visible, frame); n_seed_upd = depth_filter.finishUpdateSeeds(); seeds_finished = true; }   // wait here, as the reference does
       }
       // the frame before this one is dropped here unless it is a keyframe: its release (svoh_release_frame) is part of
@@ -344,6 +381,7 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
     out->wall_ms = now_ms() - wall0;
     fclose(fc);
     if (fk) fclose(fk);
+    if (fsc) fclose(fsc);
     out->n_done = n_done; out->sum_ms = sum_ms; out->n_kfs = kfs.size();
     for (const FramePtr& f : kfs) for (auto& sr : f->seed_ref_vec_) sr.keyframe.reset();
     if (last) for (auto& sr : last->seed_ref_vec_) sr.keyframe.reset();
@@ -419,10 +457,11 @@ void run_lockstep_group(const io::EurocSequence& seq, const std::vector<io::Gray
       if (const char* sp = getenv("SVOH_LOCKSTEP_SPECULATE")) lo.speculation = std::string(sp) == "all" ? LockstepOptions::kSpeculateAll : std::string(sp) == "never" ? LockstepOptions::kSpeculateNever : LockstepOptions::kSpeculateAsBefore;
       if (getenv("SVOH_LOCKSTEP_RESIDENT")) lo.resident_features = atoi(getenv("SVOH_LOCKSTEP_RESIDENT")) != 0;
       if (getenv("SVOH_MINI_LANDMARKS")) lo.landmarks = atoi(getenv("SVOH_MINI_LANDMARKS")) != 0;
+      if (const char* e = getenv("SVOH_MINI_SEEDS_OLD_KEYFRAMES")) lo.seeds_old_keyframes = std::string(e) == "1" || std::string(e) == "seq";   // (the engine has the one-call form only)
       FrontendLockstep fe(ctx, n, lo);
       const bool last_lap = lap + 1 == n_laps;
       std::vector<std::unique_ptr<io::TrajectoryWriter>> traj;
-      std::vector<FILE*> csv, kf_csv;
+      std::vector<FILE*> csv, kf_csv, sc_csv;
       if (last_lap)
         for (int i = 0; i < n; ++i) {
           const int s = s0 + i;
@@ -433,12 +472,20 @@ void run_lockstep_group(const io::EurocSequence& seq, const std::vector<io::Gray
           fprintf(fc, "frame,is_kf,n_aligned,n_reprojected,n_after_pose_opt,n_seeds_updated,n_converged_seeds,ms_pyramid,ms_align,ms_reproject,ms_pose,ms_seeds,ms_kf,ms_frame,n_points_optimized,n_landmarks\n");
           csv.push_back(fc);
           kf_csv.push_back(lo.log_new_features ? fopen((dir + "/keyframes.csv").c_str(), "w") : nullptr);
+          // (as the single-stream chain: the file exists when the switch is on and the stream's parameter file does not say no)
+          const bool chain_on = lo.seeds_old_keyframes && (lo.per_stream.empty() ? lo.params : lo.per_stream[(size_t)i].params).update_seeds_with_old_keyframes;
+          sc_csv.push_back(chain_on ? fopen((dir + "/seed_chain.csv").c_str(), "w") : nullptr);
+          if (chain_on && !sc_csv.back()) throw std::runtime_error("cannot write into " + dir);
+          if (sc_csv.back()) fprintf(sc_csv.back(), "frame,n_chain_frames,n_seeds,n_step_successes,n_converged_after\n");
         }
       std::vector<FrontendLockstep::RoundTimes> times;
       std::vector<std::vector<size_t>> round_of((size_t)n);   // the round in which a stream's j-th frame ran
       auto write_rows = [&]() {
         for (int i = 0; i < n; ++i) {
           if (last_lap && kf_csv[(size_t)i]) for (const FrontendLockstep::NewFeature& nf : fe.newKeyframeFeatures(i)) fprintf(kf_csv[(size_t)i], "%zu,%.17g,%.17g,%d\n", nf.k, nf.x, nf.y, nf.type);
+          if (lo.seeds_old_keyframes)
+            for (const FrontendLockstep::SeedChainRow& r : fe.seedChainRows(i))
+              if (last_lap && sc_csv[(size_t)i]) fprintf(sc_csv[(size_t)i], "%zu,%zu,%zu,%zu,%zu\n", r.k, r.n_chain_frames, r.n_seeds, r.n_step_successes, r.n_converged_after);
           for (const FrontendLockstep::FrameRow& r : fe.completedRows(i)) {
             if (!last_lap) continue;
             const FrontendLockstep::RoundTimes& t = times.at(round_of[(size_t)i].at(r.k));
@@ -499,6 +546,7 @@ void run_lockstep_group(const io::EurocSequence& seq, const std::vector<io::Gray
       }
       for (FILE* f : csv) fclose(f);
       for (FILE* f : kf_csv) if (f) fclose(f);
+      for (FILE* f : sc_csv) if (f) fclose(f);
     }
     (void)svoh_host_free(ctx, pinned);
     svoh_destroy(ctx);
