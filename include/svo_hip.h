@@ -1094,6 +1094,49 @@ int svoh_optimize_points_batch_enqueue(svoh_ctx* ctx, int n_iter, int using_bear
                                        const int32_t* obs_view, const double* obs_f, const double* pos);
 int svoh_optimize_points_batch_collect(svoh_ctx* ctx, int n_points, double* pos, int32_t* iters);
 
+/* ---- homography estimator of the mono bootstrap (csrc/init.hip; DESIGN.md, "Homography initialiser") ----
+ * Stands where vk::estimateHomography calls cv::findHomography(..., cv::RANSAC, thresh)
+ * (vikit_common/src/homography.cpp:36-56): OpenCV's random numbers, early stop and polish cannot be restated, so this
+ * is an estimator of our own whose result is a function of its inputs alone.  Per problem: n matches on the unit plane
+ * (uv_ref, uv_cur: 2 x n, host), thresh = reproj_error_thresh / |fx|, a 64-bit seed; all n_hypotheses hypotheses are run.
+ *   mix(x): x += 0x9E3779B97F4A7C15; x = (x ^ x>>30) * 0xBF58476D1CE4E5B9; x = (x ^ x>>27) * 0x94D049BB133111EB; x ^ x>>31.
+ *   Hypothesis h draws mix(seed ^ mix((h << 8) + d)) mod n for d = 0, 1, ... < 64 until it has four different indices,
+ *   builds H = B adj(A) from the four pairs (A, B: the matrices that send the projective basis to the ref and the cur
+ *   points; degenerate when a lambda is below 1e-9 or not a number), divides it by its Frobenius norm and counts the
+ *   matches with dx^2 + dy^2 < thresh^2 w^2, where (x, y, w) = H (u_ref, v_ref, 1), dx = x - u_cur w, dy = y - v_cur w.
+ *   The largest count wins, the lowest h among equals.  The winner is divided by H[8] (unless |H[8]| < 1e-12: then it
+ *   stays as it is and is not refined) and refined by at most 10 Gauss-Newton iterations over its 8 free entries on the
+ *   winner's inliers, residual (x/w - u_cur, y/w - v_cur); it stops at max|step| < 1e-10, a step that is not finite is
+ *   not taken.  The mask and n_inliers are the inlier rule once more with the refined H.
+ * No hypothesis that is not degenerate, or a winning count below 4 (always so for n < 4): status
+ * SVOH_HOMOGRAPHY_NO_MODEL and every other output zero.  n > 1024: SVOH_ERR_INVALID_ARGUMENT, nothing written.
+ * masks: one byte per match, the problems' one after the other.  Blocking; one workgroup per problem, and a problem's
+ * result does not depend on what else is in the batch. */
+enum { SVOH_HOMOGRAPHY_OK = 0, SVOH_HOMOGRAPHY_NO_MODEL = 1 };
+typedef struct svoh_init_options {
+  int32_t n_hypotheses;           /* K; HomographyInitHip uses 2000 */
+  int32_t reserved;
+} svoh_init_options;
+typedef struct svoh_homography_problem {
+  int32_t n;
+  int32_t reserved;
+  const double* uv_ref;           /* 2 x n */
+  const double* uv_cur;           /* 2 x n */
+  double thresh;
+  uint64_t seed;
+} svoh_homography_problem;
+typedef struct svoh_homography_result {
+  double H[9];                    /* row-major, cur <- ref, H[8] = 1 */
+  int32_t best_hypothesis;
+  int32_t n_inliers_hypothesis;   /* the winner's count, before the refinement */
+  int32_t n_inliers;              /* after it: the number of ones in the mask */
+  int32_t refine_iters;           /* Gauss-Newton iterations started */
+  int32_t status;                 /* SVOH_HOMOGRAPHY_* */
+  int32_t reserved;
+} svoh_homography_result;
+int svoh_homography_ransac_batch(svoh_ctx* ctx, const svoh_init_options* options, int n_problems,
+                                 const svoh_homography_problem* problems, svoh_homography_result* results, uint8_t* masks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,34 @@ def default_pose_options(cam=None, reproj_thresh_px=2.0, **kw):
     return o
 
 
+SVOH_HOMOGRAPHY_OK, SVOH_HOMOGRAPHY_NO_MODEL = 0, 1
+SVOH_ERR_INVALID_ARGUMENT = -1
+
+
+class svoh_init_options(C.Structure):
+    _fields_ = [("n_hypotheses", C.c_int32), ("reserved", C.c_int32)]
+
+
+class svoh_homography_problem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("uv_ref", C.c_void_p), ("uv_cur", C.c_void_p),
+                ("thresh", C.c_double), ("seed", C.c_uint64)]
+
+
+class svoh_homography_result(C.Structure):
+    _fields_ = [("H", C.c_double * 9), ("best_hypothesis", C.c_int32), ("n_inliers_hypothesis", C.c_int32),
+                ("n_inliers", C.c_int32), ("refine_iters", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+def default_init_options(**kw):
+    """The homography initialiser's estimator (include/svo_hip.h, svoh_homography_ransac_batch): 2000 hypotheses."""
+    o = svoh_init_options(n_hypotheses=2000)
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
 class svoh_detector_options(C.Structure):
     _fields_ = [("cell_size", C.c_int32), ("max_level", C.c_int32), ("min_level", C.c_int32), ("border", C.c_int32),
                 ("detect_edgelets", C.c_int32), ("reserved", C.c_int32),
@@ -309,6 +337,8 @@ EXPORTS = [
     "svoh_matcher_stage", "svoh_detect_cells_batch", "svoh_detect_cells_batch_enqueue", "svoh_detect_cells_batch_collect", "svoh_detect_fill_features", "svoh_histogram_angle_bins", "svoh_features_upload", "svoh_features_release", "svoh_select_matches_batch",
     # camera masks: resident on the device, applied between the two phases of the batched detector
     "svoh_mask_upload", "svoh_mask_release", "svoh_detect_cells_batch_masked", "svoh_detect_cells_batch_masked_enqueue",
+    # mono bootstrap: the homography estimator (csrc/init.hip)
+    "svoh_homography_ransac_batch",
 ]
 
 
@@ -457,6 +487,8 @@ def load(path=None):
     lib.svoh_mask_release.argtypes = [C.c_void_p, svoh_mask_t]
     lib.svoh_detect_cells_batch_masked.argtypes = [C.c_void_p, C.c_int, P(svoh_frame_t), P(svoh_detector_options), C.c_void_p, P(svoh_mask_t), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.svoh_detect_cells_batch_masked_enqueue.argtypes = [C.c_void_p, C.c_int, P(svoh_frame_t), P(svoh_detector_options), C.c_void_p, P(svoh_mask_t)]
+    lib.svoh_homography_ransac_batch.argtypes = [C.c_void_p, P(svoh_init_options), C.c_int, P(svoh_homography_problem),
+                                                 P(svoh_homography_result), C.c_void_p]
     lib.svoh_histogram_angle_bins.argtypes = [C.c_void_p, C.c_int, P(svoh_frame_t), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.svoh_detect_fill_features.argtypes = [P(svoh_detector_options), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int32)]

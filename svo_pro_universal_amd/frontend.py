@@ -556,6 +556,31 @@ def _optimize_points(self, views, obs_begin, obs_view, obs_f, pos, n_iter=5, usi
     return out, iters[:n]
 
 
+def _homography_ransac(self, problems, options=None):
+    """svoh_homography_ransac_batch: the homography estimator of the mono bootstrap for a batch of problems.
+    problems: list of (uv_ref [n,2], uv_cur [n,2], thresh, seed) -- matches on the unit plane, thresh = px / |fx|.
+    Returns (results: list of svoh_homography_result, masks: list of uint8 arrays [n])."""
+    opt = options if options is not None else capi.default_init_options()
+    n_pb = len(problems)
+    pbs = (capi.svoh_homography_problem * max(1, n_pb))()
+    res = (capi.svoh_homography_result * max(1, n_pb))()
+    keep, sizes = [], []
+    for i, (uv_ref, uv_cur, thresh, seed) in enumerate(problems):
+        a = np.ascontiguousarray(uv_ref, dtype=np.float64).reshape(-1, 2)
+        b = np.ascontiguousarray(uv_cur, dtype=np.float64).reshape(-1, 2)
+        if a.shape != b.shape:
+            raise ValueError("uv_ref and uv_cur differ in size")
+        keep += [a, b]
+        sizes.append(a.shape[0])
+        pbs[i].n = a.shape[0]
+        pbs[i].uv_ref, pbs[i].uv_cur = a.ctypes.data, b.ctypes.data
+        pbs[i].thresh, pbs[i].seed = float(thresh), int(seed) & 0xFFFFFFFFFFFFFFFF
+    masks = np.zeros(max(1, sum(sizes)), np.uint8)
+    self._check(self.lib.svoh_homography_ransac_batch(self.h, C.byref(opt), n_pb, pbs, res, masks.ctypes.data))
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+    return [res[i] for i in range(n_pb)], [masks[off[i]:off[i + 1]].copy() for i in range(n_pb)]
+
+
 def _detect_features(self, opt, frame, width, height, occupancy=None, mask=None, max_n_features=None):
     """svoh_detect_features: dict(px [n,2], score, level, grad [n,2], type) like FastGradDetector::detect."""
     n_cells = int(np.ceil(width / opt.cell_size)) * int(np.ceil(height / opt.cell_size))
@@ -650,6 +675,7 @@ Context.detect_cells_batch_collect = _detect_cells_batch_collect
 Context.detect_features = _detect_features
 Context.optimize_pose = _optimize_pose
 Context.optimize_points = _optimize_points
+Context.homography_ransac = _homography_ransac
 Context.klt_track_batch = _klt_track_batch
 Context.klt_track_indexed = _klt_track_indexed
 Context.update_seeds_device = _update_seeds_device

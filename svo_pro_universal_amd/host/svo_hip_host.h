@@ -411,6 +411,10 @@ class FeatureTrackerHip {
   const FeatureTracks& getActiveTracks(size_t frame_index) const { return active_tracks_.at(frame_index); }
   const FeatureTracks& getTerminatedTracks(size_t frame_index) const { return terminated_tracks_.at(frame_index); }
   size_t getTotalActiveTracks() const;
+  // feature_tracker.cpp:202-226: per frame of the bundle the number of active tracks and the percentile of their disparities
+  // (feature_tracking_utils::getTracksDisparityPercentile); the bundle of the first observation of the first active track
+  void getNumTrackedAndDisparityPerFrame(double pivot_ratio, std::vector<size_t>* num_tracked, std::vector<double>* disparity) const;
+  FrameBundle::Ptr getOldestFrameInTrack(size_t frame_index) const;
   void resetActiveTracks() { for (auto& t : active_tracks_) t.clear(); }
   void resetTerminatedTracks() { for (auto& t : terminated_tracks_) t.clear(); }
   void reset() { resetActiveTracks(); resetTerminatedTracks(); }

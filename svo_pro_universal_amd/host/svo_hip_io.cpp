@@ -367,6 +367,20 @@ FrontendParams frontendParamsFromYaml(const YamlNode& node)
   p.depth_filter.scan_epi_unit_sphere = node["scan_epi_unit_sphere"].asBool(false);
   p.poseoptim_using_unit_sphere = node["poseoptim_using_unit_sphere"].asBool(false);
   p.update_seeds_with_old_keyframes = node["update_seeds_with_old_keyframes"].asBool(true);
+  // the initialiser's keys (svo_factory.cpp:123, 178-195)
+  p.map_scale = node["map_scale"].asDouble(1.0);
+  p.init.init_min_features = (size_t)node["init_min_features"].asInt(100);
+  p.init.init_min_tracked = (size_t)node["init_min_tracked"].asInt(80);
+  p.init.init_min_inliers = (size_t)node["init_min_inliers"].asInt(70);
+  p.init.init_min_disparity = node["init_min_disparity"].asDouble(40.0);
+  p.init.init_min_features_factor = node["init_min_features_factor"].asDouble(2.0);
+  p.init.reproj_error_thresh = node["reproj_err_thresh"].asDouble(2.0);
+  p.init.init_disparity_pivot_ratio = node["init_disparity_pivot_ratio"].asDouble(0.5);
+  p.init.init_method = node["init_method"].asString("FivePoint");
+  if (p.init.init_method == "Homography") p.init.init_type = InitializerType::kHomography;
+  else if (p.init.init_method == "TwoPoint") p.init.init_type = InitializerType::kTwoPoint;
+  else if (p.init.init_method == "OneShot") p.init.init_type = InitializerType::kOneShot;
+  else p.init.init_type = InitializerType::kFivePoint;   // also what the factory leaves for a method it does not know
   p.depth_filter.affine_est_offset = node["depth_filter_affine_est_offset"].asBool(true);
   p.depth_filter.affine_est_gain = node["depth_filter_affine_est_gain"].asBool(false);
   p.max_n_seeds_per_frame = (int)((double)node["max_fts"].asInt(120) * node["max_seeds_ratio"].asDouble(3.0));

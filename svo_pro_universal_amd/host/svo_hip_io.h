@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "svo_hip_host.h"
+#include "svo_hip_init.h"
 
 namespace svo_hip {
 namespace io {
@@ -84,6 +85,11 @@ struct FrontendParams {
   // frame and the overlap keyframes (frame_handler_mono.cpp:218-225).  Parsed only: the chains act on it where they are asked to
   // (svoh_mini_frontend: SVOH_MINI_SEEDS_OLD_KEYFRAMES; LockstepOptions::seeds_old_keyframes)
   bool update_seeds_with_old_keyframes = true;
+  // the initialiser (svo_factory.cpp:178-195: init_min_features, init_min_tracked, init_min_inliers, init_min_disparity,
+  // init_min_features_factor, reproj_err_thresh, init_disparity_pivot_ratio, init_method) and map_scale (:123), the depth prior
+  // processFirstFrame hands it.  Parsed only: svoh_mini_frontend acts on them under SVOH_MINI_BOOTSTRAP.
+  InitializationOptions init;
+  double map_scale = 1.0;
 };
 FrontendParams frontendParamsFromYaml(const YamlNode& node);
 FrontendParams loadFrontendParams(const std::string& param_yaml_path);

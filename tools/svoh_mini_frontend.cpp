@@ -31,6 +31,15 @@
 // frame (the comparison arm: same bytes).  Writes <out>/seed_chain.csv (frame, n_chain_frames, n_seeds, n_step_successes,
 // n_converged_after).  Unset: the tool behaves and prints exactly as without the switch.  The lock-step mode takes the same
 // switch (LockstepOptions::seeds_old_keyframes: one call per round for all streams that made a keyframe).
+// SVOH_MINI_BOOTSTRAP=1 (one stream, threads mode, init_method: Homography in the parameter file -- anything else is refused by
+// name): the chain starts from images alone, as FrameHandlerMono::processFirstFrame does (frame_handler_mono.cpp:64-118).  The
+// first frame gets the command line's T_f_w(0); frames are fed to HomographyInitHip (host/svo_hip_init.h; depth prior =
+// depth_mean, the scene depth at the frame that succeeds; depth_min and depth_max are not used) until it succeeds; then both
+// frames become keyframes carrying the triangulated landmarks, the new frame gets seeds with (median, 0.5 min, 1.5 median) of
+// frame_utils::getSceneDepth, the seeds are updated once, and the chain above goes on from the next frame.  trajectory.txt
+// holds the reference frame and every frame from the success on; frontend.csv has a row per frame from the success on;
+// <out>/bootstrap.csv has one line per initialiser call: frame, result, n_tracked, disparity, n_inliers, n_triangulated,
+// scale, ms_ransac.  Unset: the tool prints and writes exactly what it does without the switch.
 // n_streams > 1 (independent camera streams need no exchange): that many host threads, each
 // with its own svoh_ctx (own HIP stream) and its own copy of the chain's state, run the same sequence side by side on
 // ONE GPU; stream k > 0 writes into <out>/stream<k>/.  At EuRoC sizes a stream keeps the GPU busy for a small part
@@ -200,14 +209,17 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
     }
     std::unique_ptr<DepthFilterHip> depth_filter_seq;   // the comparison arm's calls (the chain's own filter may have an update in flight)
     if (seeds_old_kfs == 2) depth_filter_seq.reset(new DepthFilterHip(ctx, params.depth_filter));
-    auto make_keyframe = [&](const FramePtr& f, const FramePtr& last_frame) {
+    // scene_depth != NULL (the bootstrap's second keyframe): its features carry the initialiser's landmarks already -- nothing to
+    // upgrade -- and its seeds start from the scene depth {min, mean, max} instead of the command line's prior
+    auto make_keyframe = [&](const FramePtr& f, const FramePtr& last_frame, const float* scene_depth = nullptr) {
       // the frame handler's step at a new keyframe (frame_handler_mono.cpp:186): the seeds this frame's features hang on become
       // landmarks (the seed update in flight, if any, leaves such a seed alone when it is written back: DepthFilterHip)
-      if (landmarks_on) upgradeSeedsToFeatures(ctx, f, &next_point_id);
+      if (landmarks_on && !scene_depth) upgradeSeedsToFeatures(ctx, f, &next_point_id);
       detector.resetGrid();
       detector.fillGridWithKeypoints(f->px_vec_, f->num_features_);
       const size_t n_old = f->num_features_;
-      depth_filter_utils::initializeSeeds(f, detector, (size_t)params.max_n_seeds_per_frame, depth_min, depth_max, depth_mean);
+      depth_filter_utils::initializeSeeds(f, detector, (size_t)params.max_n_seeds_per_frame, scene_depth ? scene_depth[0] : depth_min, scene_depth ? scene_depth[2] : depth_max,
+                                          scene_depth ? scene_depth[1] : depth_mean);
       // bootstrap stand-in for the initialiser's landmarks: a keyframe's own new seeds are usable for the
       // alignment of the next frame at their current depth estimate (self reference)
       for (size_t i = n_old; i < f->num_features_; ++i) { f->seed_ref_vec_[i].keyframe = f; f->seed_ref_vec_[i].seed_id = (int)i; }
@@ -267,6 +279,17 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
               n_seed_upd, n_conv, row.ms[0], row.ms[1], row.ms[2], row.ms[3], row.ms[4], row.ms[5], row.ms[6], row.n_struct, row.n_landmarks);
       row.valid = false;
     };
+    // SVOH_MINI_BOOTSTRAP: the initialiser in front of the chain
+    const bool bootstrap = getenv("SVOH_MINI_BOOTSTRAP") != nullptr && atoi(getenv("SVOH_MINI_BOOTSTRAP")) != 0;
+    std::unique_ptr<HomographyInitHip> initializer;
+    FILE* fb = nullptr;
+    bool initialised = !bootstrap;
+    if (bootstrap) {
+      initializer.reset(new HomographyInitHip(ctx, params.init, params.tracker, std::make_shared<DetectorHip>(ctx, params.detector, cam.width, cam.height)));
+      fb = fopen((out_dir + "/bootstrap.csv").c_str(), "w");
+      if (!fb) throw std::runtime_error("cannot write into " + out_dir);
+      fprintf(fb, "frame,result,n_tracked,disparity,n_inliers,n_triangulated,scale,ms_ransac\n");
+    }
     StructureBatch structure;
     bool structure_in_flight = false;
     auto finish_structure = [&]() {
@@ -300,7 +323,37 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
       bool seeds_finished = false;
       double t2 = t1, t3 = t1, t4 = t1, t5 = t1;
       bool is_kf = false;
-      if (k == 0) {
+      if (!initialised) {
+        // processFirstFrame (frame_handler_mono.cpp:64-118)
+        frame->T_f_w_ = T0;   // (every frame starts from the pose of the one before: the first frame's, until there is a map)
+        if (!initializer->have_depth_prior_) initializer->setDepthPrior(depth_mean);
+        FrameBundle::Ptr b_cur(new FrameBundle);
+        b_cur->frames_.push_back(frame);
+        if (svoh_set_kernel_timing(ctx, 1) != SVOH_OK) throw std::runtime_error(svoh_last_error_string(ctx));   // (ms_ransac: the estimator's kernel time)
+        const InitResult res = initializer->addFrameBundle(b_cur);
+        if (svoh_set_kernel_timing(ctx, 0) != SVOH_OK) throw std::runtime_error(svoh_last_error_string(ctx));
+        const HomographyInitHip::Statistics& st = initializer->stats_;
+        fprintf(fb, "%zu,%s,%zu,%.6f,%zu,%zu,%.9g,%.4f\n", k, res == InitResult::kSuccess ? "kSuccess" : res == InitResult::kFailure ? "kFailure" : "kTracking", st.n_tracked,
+                st.disparity, st.n_inliers, st.n_triangulated, st.scale, st.ms_ransac);
+        if (res != InitResult::kSuccess) continue;   // kTracking; kFailure has reset the initialiser: the next frame starts over
+        // both frames become keyframes and carry the landmarks (:81-98, 100, 111)
+        const FramePtr ref = initializer->frames_ref_->at(0);
+        for (size_t i = 0; i < frame->num_features_; ++i) if (frame->landmark_vec_[i]) next_point_id = std::max(next_point_id, frame->landmark_vec_[i]->id_ + 1);
+        kfs.push_back(ref);
+        // getSceneDepth of the new frame, its seeds with (median, 0.5 min, 1.5 median) (:101-105), updated once (:107).  The frame
+        // handler updates them with the frame before, which has no pose of its own there; this harness takes the other frame that
+        // has one, the reference frame
+        double d_med = 0, d_min = 0, d_max = 0;
+        if (!frame_utils::getSceneDepth(*frame, d_med, d_min, d_max)) throw std::runtime_error("bootstrap: the new frame has no landmarks");
+        const float scene_depth[3] = { (float)(0.5 * d_min), (float)d_med, (float)(1.5 * d_med) };
+        make_keyframe(frame, nullptr, scene_depth);
+        depth_filter.updateSeeds({ frame }, ref);
+        initializer->reset();
+        initialised = true;
+        is_kf = true;
+        traj.write(seq.cam_ts[order[(size_t)ref->id_]], svoh::inverse(ref->T_f_w_));
+        t2 = t3 = t4 = t5 = now_ms();
+      } else if (k == 0) {
         frame->T_f_w_ = T0;
         make_keyframe(frame, nullptr);   // (no last frame: no step)
         is_kf = true;
@@ -365,17 +418,20 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
       }
       // the frame before this one is dropped here unless it is a keyframe: its release (svoh_release_frame) is part of
       // the frame's time
+      const bool last_was_chain_frame = last != nullptr;   // (false for the bootstrap's success frame too: nothing of it is in flight)
       last = frame;
       const double t6 = now_ms();
       traj.write(seq.cam_ts[order[k]], svoh::inverse(frame->T_f_w_));
-      row.valid = true; row.finished = seeds_finished || k == 0; row.n_seed_upd = n_seed_upd; row.k = k; row.is_kf = (int)is_kf; row.n_aligned = n_aligned; row.n_reproj = n_reproj; row.n_pose = n_pose;
+      row.valid = true; row.finished = seeds_finished || k == 0 || !last_was_chain_frame; row.n_seed_upd = n_seed_upd; row.k = k; row.is_kf = (int)is_kf; row.n_aligned = n_aligned; row.n_reproj = n_reproj; row.n_pose = n_pose;
       row.n_struct = n_struct; row.n_landmarks = 0;
       for (size_t i = 0; i < frame->num_features_ && i < frame->landmark_vec_.size(); ++i) row.n_landmarks += frame->landmark_vec_[i] != nullptr;
       row.ms[0] = t0f - t0; row.ms[1] = t2 - t1; row.ms[2] = t3 - t2; row.ms[3] = t4 - t3; row.ms[4] = t5 - t4; row.ms[5] = t6 - t5;
       row.ms[6] = t6 - t0;   // the frame as the caller's clock sees it, the previous frame's seed write-back included
       if (sync_flow) finish_row();
-      if (k > 0) { sum_ms += t6 - t0; ++n_done; }
+      if (k > 0 && last_was_chain_frame) { sum_ms += t6 - t0; ++n_done; }
     }
+    if (fb) fclose(fb);
+    if (bootstrap && !initialised) throw std::runtime_error("bootstrap: the initialiser did not succeed on this sequence");
     finish_structure();
     finish_row();
     out->wall_ms = now_ms() - wall0;
@@ -578,6 +634,12 @@ int main(int argc, char** argv)
     const bool lockstep = argc > 18 && std::string(argv[18]) == "lockstep";
     if (argc > 18 && !lockstep && std::string(argv[18]) != "threads") throw std::runtime_error("mode must be threads or lockstep");
     if (n_streams < 1 || n_streams > (lockstep ? 256 : 64)) throw std::runtime_error("n_streams out of range");
+    if (getenv("SVOH_MINI_BOOTSTRAP") && atoi(getenv("SVOH_MINI_BOOTSTRAP")) != 0) {
+      if (lockstep) throw std::runtime_error("SVOH_MINI_BOOTSTRAP: the lock-step mode has no initialiser");
+      if (n_streams != 1 || !specs.empty()) throw std::runtime_error("SVOH_MINI_BOOTSTRAP: one stream, no SVOH_MINI_SPEC");
+      if (params.init.init_method != "Homography")
+        throw std::runtime_error("SVOH_MINI_BOOTSTRAP: init_method " + params.init.init_method + " is not built (only Homography is)");
+    }
     std::vector<io::GrayImage> images;
     for (size_t k = 0; k < seq.size() && k < max_frames; ++k) images.push_back(io::readPngGray(seq.cam0_files[k]));
     if (lockstep) {
