@@ -137,6 +137,41 @@ struct MatcherState {
 #define SVOH_MSTAMP(m, k) do { } while (0)
 #endif
 
+// a fresh Matcher for the unit's next match; the patch, the lane's row and the work counters run on
+__device__ __forceinline__ void matcher_state_rearm(MatcherState& m, bool align_1d)
+{
+  m.h_inv = 0.0; m.search_level = 0; m.reject = false;
+  m.align_1d = align_1d;
+  m.A[0] = m.A[1] = m.A[2] = m.A[3] = 0.0;
+  m.px_cur[0] = m.px_cur[1] = 0.0;
+  m.f_cur = { 0.0, 0.0, 0.0 };
+  m.epi_dir[0] = m.epi_dir[1] = 0.0;
+}
+
+// a unit's matcher state before its first match: its patch in LDS, the lane's row of it (eight lanes per unit; 0 otherwise)
+__device__ __forceinline__ void matcher_state_reset(MatcherState& m, unsigned char* pwb, int sub, bool align_1d)
+{
+  m.pwb = pwb;
+  m.sub = sub;
+  m.n_warp = 0; m.n_zmssd = 0; m.n_align_it = 0;
+#ifdef SVOH_SEED_STAMPS
+  m.t[0] = m.t[1] = m.t[2] = m.t[3] = 0; m.tlast = clock64();
+#endif
+  matcher_state_rearm(m, align_1d);
+}
+
+// the launch geometries with 64-thread workgroups (G8: 0 one lane per unit, 1 eight lanes per unit, 3 one wave per unit): the
+// thread's slot in its workgroup's patch buffer, its unit, and whether this lane is the one that reports the unit's results
+struct UnitOfThread { int unit, i; bool reporter; };
+template <int G8>
+__device__ __forceinline__ UnitOfThread unit_of_thread(int block)
+{
+  const int unit = G8 == 1 ? (int)(threadIdx.x >> 3) : (G8 == 3 ? 0 : (int)threadIdx.x);
+  const int i = block * (G8 == 1 ? 8 : (G8 == 3 ? 1 : 64)) + unit;
+  const bool reporter = G8 == 0 || (G8 == 1 && (threadIdx.x & 7) == 0) || (G8 == 3 && (threadIdx.x & 63) == 0);
+  return { unit, i, reporter };
+}
+
 __device__ __forceinline__ int patch_at(const unsigned char* pwb, int r) { return pwb[((r >> 3) + 1) * 10 + (r & 7) + 1]; }
 
 __device__ __forceinline__ void normalize2(double& x, double& y)
@@ -1951,6 +1986,7 @@ __device__ __forceinline__ void match_direct_body(const MatcherArgs& a, int bloc
     reinterpret_cast<uint4*>(a.unit_counts)[i] = make_uint4(0u, 0u, 0u, 0u);
     return;
   }
+  // (not matcher_state_reset: match_direct_kernel has to disassemble as it did, and through the function it does not)
   MatcherState m;
   m.pwb = s_pwb + unit * kPwbStride;
   m.sub = G8 ? (int)(threadIdx.x & 7) : 0;
@@ -1982,16 +2018,110 @@ __global__ __launch_bounds__(64) void match_direct_kernel(const MatcherArgs a)
   match_direct_body<G8>(a, (int)blockIdx.x, s_pwb);
 }
 
-// DepthFilter::updateSeeds (depth_filter.cpp:200-233) + depth_filter_utils::updateSeed (:367-499)
+// ---- depth_filter_utils::updateSeed (depth_filter.cpp:367-499): gate, apply and the step built from them ----------------
+// a seed's convergence threshold on sigma2 (depth_filter.cpp:371-376)
+__device__ __forceinline__ double seed_convergence_thresh(const svoh_depth_filter_options& dopt, int type)
+{
+  if (type == SVOH_FT_MAPPOINT_SEED || type == SVOH_FT_MAPPOINT_SEED_CONVERGED) return dopt.mappoint_convergence_sigma2_thresh;
+  return dopt.seed_convergence_sigma2_thresh;
+}
+
+// The gate: everything updateSeed checks before it calls the matcher, in two halves with T_cur_ref between them.
+// First the seed's type and the frames: isSeed, the frame itself, outliers, converged seeds under check_convergence.
+__device__ __forceinline__ bool seed_gate_type(const svoh_depth_filter_options& dopt, const DevFrameView& ref, const DevFrameView& cur, int type)
+{
+  if (!(type < 6)) return false;  // isSeed
+  if (cur.id == ref.id) return false;
+  if (type == SVOH_FT_OUTLIER) return false;
+  if ((type == SVOH_FT_CORNER_SEED_CONVERGED || type == SVOH_FT_EDGELET_SEED_CONVERGED ||
+       type == SVOH_FT_MAPPOINT_SEED_CONVERGED) && dopt.check_convergence)
+    return false;
+  return true;
+}
+
+// ... then the projection into the current image and its 9-pixel border.  state / f: the seed's four and three doubles, in
+// memory or in registers.
+__device__ __forceinline__ bool seed_gate_visible(const svoh_depth_filter_options& dopt, const DevFrameView& cur, const Rigid& T_cur_ref,
+                                                  const double* state, const double* f)
+{
+  if (!dopt.check_visibility) return true;
+  const double depth = 1.0 / state[0];
+  const Vec3 p = { depth * f[0], depth * f[1], depth * f[2] };
+  double px, py;
+  project3(cur.cam, transform(T_cur_ref, p), px, py);
+  if (!(px >= 0.0 && py >= 0.0 && px < (double)cur.cam.width && py < (double)cur.cam.height)) return false;
+  const int pxi0 = (int)px, pxi1 = (int)py;
+  const int boundary = 9;
+  return pxi0 >= boundary && pxi1 >= boundary && pxi0 < cur.cam.width - boundary && pxi1 < cur.cam.height - boundary;
+}
+
+// The whole gate; T_cur_ref comes out for the search and for seed_update_apply.
+__device__ __forceinline__ bool seed_update_gate(const svoh_depth_filter_options& dopt, const DevFrameView& ref, const DevFrameView& cur,
+                                                 int type, const double* state, const double* f, Rigid& T_cur_ref)
+{
+  if (!seed_gate_type(dopt, ref, cur, type)) return false;
+  T_cur_ref = T_cur_ref_of(ref, cur);
+  return seed_gate_visible(dopt, cur, T_cur_ref, state, f);
+}
+
+// After a successful match at `depth`: tau, the filter update, the outlier mark and the promotion to *_CONVERGED against
+// seed_mu_range / cur_thresh (seed_convergence_thresh of the type the seed had before).
+// Returns updateSeed's value; st is what the filter left in either case.
+__device__ __forceinline__ bool seed_update_apply(const svoh_depth_filter_options& dopt, const DevFrameView& ref, const Rigid& T_cur_ref,
+                                                  const Vec3& f, double depth, double cur_thresh, double (&st)[4], int& type)
+{
+  const double depth_sigma = compute_tau(inverse(T_cur_ref), f, depth, dopt.px_error_angle);
+  const double z = 1.0 / depth;
+  const double sg = 0.5 * (1.0 / fmax(0.000000000001, depth - depth_sigma) - 1.0 / (depth + depth_sigma));
+  const double tau2 = sg * sg;
+  bool ok;
+  if (dopt.use_vogiatzis_update) ok = update_filter_vogiatzis(z, tau2, ref.seed_mu_range, st);
+  else ok = update_filter_gaussian(z, tau2, st);
+  if (!ok) { type = SVOH_FT_OUTLIER; return false; }
+  const double thresh = ref.seed_mu_range / cur_thresh;
+  if (st[1] < thresh * thresh) {
+    if (type == SVOH_FT_CORNER_SEED) type = SVOH_FT_CORNER_SEED_CONVERGED;
+    else if (type == SVOH_FT_EDGELET_SEED) type = SVOH_FT_EDGELET_SEED_CONVERGED;
+    else if (type == SVOH_FT_MAPPOINT_SEED) type = SVOH_FT_MAPPOINT_SEED_CONVERGED;
+  }
+  return true;
+}
+
+// One updateSeed of a unit against `cur`, state and type in registers: returns updateSeed's value; res = the matcher's
+// result, or SVOH_MATCH_NOT_RUN when the gate closed before it.  m: reset by the caller before the unit's first step.
+template <int G8>
+__device__ __forceinline__ bool seed_update_step(const MatcherArgs& a, MatcherState& m, const DevFrameView& ref, const DevFrameView& cur,
+                                                 double pxr, double pyr, const Vec3& f, double gx, double gy, int level,
+                                                 double (&st)[4], int& type, int& res)
+{
+  res = SVOH_MATCH_NOT_RUN;
+  Rigid T_cur_ref;
+  // (the threshold of the type the seed has now; apply may change the type)
+  const double cur_thresh = seed_convergence_thresh(a.dopt, type);
+  const double fv[3] = { f.x, f.y, f.z };
+  if (!seed_update_gate(a.dopt, ref, cur, type, st, fv, T_cur_ref)) return false;
+  matcher_state_rearm(m, type == SVOH_FT_EDGELET_SEED || type == SVOH_FT_EDGELET_SEED_CONVERGED);
+  double depth = 0.0;
+  const double inv_min = st[0] + sqrt(st[1]);
+  const double inv_max = fmax(st[0] - sqrt(st[1]), 0.00000001);
+  res = find_epipolar_match_direct<G8>(m, a.mopt, ref, cur, T_cur_ref, pxr, pyr, f, gx, gy, level, type, st[0], inv_min, inv_max, depth);
+  if (res != SVOH_MATCH_SUCCESS) {
+    if (!m.reject) st[3] = st[3] + 1;  // seed::increaseOutlierProbability
+    return false;
+  }
+  return seed_update_apply(a.dopt, ref, T_cur_ref, f, depth, cur_thresh, st, type);
+}
+
+// DepthFilter::updateSeeds (depth_filter.cpp:200-233): gate, search and apply per unit, state and type in memory.  Only the
+// reporting lane goes on behind the search, so the step is spelled out here, not seed_update_step (which every lane runs through)
 // G8: 0 one lane per unit, 1 eight lanes per unit, 3 one wave per unit (scan 64 steps at a time)
 template <int G8>
 __device__ __forceinline__ void update_seeds_body(const MatcherArgs& a, int block, unsigned char* s_pwb)
 {
-  const int unit = G8 == 1 ? (int)(threadIdx.x >> 3) : (G8 == 3 ? 0 : (int)threadIdx.x);
-  const int i = block * (G8 == 1 ? 8 : (G8 == 3 ? 1 : 64)) + unit;
+  const UnitOfThread u = unit_of_thread<G8>(block);
+  const int i = u.i;
   if (i >= a.n) return;
-  const bool reporter = G8 == 0 || (G8 == 1 && (threadIdx.x & 7) == 0) || (G8 == 3 && (threadIdx.x & 63) == 0);
-  if (reporter) {
+  if (u.reporter) {
     a.success[i] = 0;
     if (a.result) a.result[i] = SVOH_MATCH_NOT_RUN;
     // units that are not run: zeros in the optional outputs (the launch does not clear the output block; a unit that
@@ -2003,49 +2133,25 @@ __device__ __forceinline__ void update_seeds_body(const MatcherArgs& a, int bloc
     reinterpret_cast<uint4*>(a.unit_counts)[i] = make_uint4(0u, 0u, 0u, 0u);
   }
   if (!feature_indices_ok(a, i)) return;
-  const int type = a.type[i];
-  if (!(type < 6)) return;  // isSeed
-  double cur_thresh = a.dopt.seed_convergence_sigma2_thresh;
-  if (type == SVOH_FT_MAPPOINT_SEED || type == SVOH_FT_MAPPOINT_SEED_CONVERGED)
-    cur_thresh = a.dopt.mappoint_convergence_sigma2_thresh;
+  const int type0 = a.type[i];
   const DevFrameView& ref = a.ref_frames[a.ref_frame_idx[i]];
   const DevFrameView& cur = a.cur_frame[a.cur_frame_idx ? a.cur_frame_idx[i] : 0];
-  if (cur.id == ref.id) return;
-  if (type == SVOH_FT_OUTLIER) return;
-  if ((type == SVOH_FT_CORNER_SEED_CONVERGED || type == SVOH_FT_EDGELET_SEED_CONVERGED ||
-       type == SVOH_FT_MAPPOINT_SEED_CONVERGED) && a.dopt.check_convergence)
-    return;
+  const double cur_thresh = seed_convergence_thresh(a.dopt, type0);
+  // (the gate's halves with T_cur_ref computed ahead of both: between them, as in seed_update_gate, update_seeds_kernel<3>
+  // spills an SGPR it did not spill before; profiles/matcher_refactor_resources.txt)
+  const Rigid T_cur_ref = T_cur_ref_of(ref, cur);
+  if (!seed_gate_type(a.dopt, ref, cur, type0) || !seed_gate_visible(a.dopt, cur, T_cur_ref, &a.state[4 * i], &a.f[3 * i])) return;
   double st[4] = { a.state[4 * i], a.state[4 * i + 1], a.state[4 * i + 2], a.state[4 * i + 3] };
   const Vec3 f = { a.f[3 * i], a.f[3 * i + 1], a.f[3 * i + 2] };
-  const Rigid T_cur_ref = T_cur_ref_of(ref, cur);
-  if (a.dopt.check_visibility) {
-    const double depth = 1.0 / st[0];
-    const Vec3 p = { depth * f.x, depth * f.y, depth * f.z };
-    double px, py;
-    project3(cur.cam, transform(T_cur_ref, p), px, py);
-    if (!(px >= 0.0 && py >= 0.0 && px < (double)cur.cam.width && py < (double)cur.cam.height)) return;
-    const int pxi0 = (int)px, pxi1 = (int)py;
-    const int boundary = 9;
-    if (!(pxi0 >= boundary && pxi1 >= boundary && pxi0 < cur.cam.width - boundary && pxi1 < cur.cam.height - boundary)) return;
-  }
   MatcherState m;
-  m.pwb = s_pwb + unit * kPwbStride;
-  m.sub = G8 ? (int)(threadIdx.x & 7) : 0;
-  m.h_inv = 0.0; m.search_level = 0; m.reject = false;
-  m.n_warp = 0; m.n_zmssd = 0; m.n_align_it = 0;
-  m.align_1d = (type == SVOH_FT_EDGELET_SEED || type == SVOH_FT_EDGELET_SEED_CONVERGED);
-  m.A[0] = m.A[1] = m.A[2] = m.A[3] = 0.0;
-  m.px_cur[0] = m.px_cur[1] = 0.0;
-  m.f_cur = { 0.0, 0.0, 0.0 };
-#ifdef SVOH_SEED_STAMPS
-  m.t[0] = m.t[1] = m.t[2] = m.t[3] = 0; m.tlast = clock64();
-#endif
+  matcher_state_reset(m, s_pwb + u.unit * kPwbStride, G8 ? (int)(threadIdx.x & 7) : 0,
+                      type0 == SVOH_FT_EDGELET_SEED || type0 == SVOH_FT_EDGELET_SEED_CONVERGED);
   double depth = 0.0;
   const double inv_min = st[0] + sqrt(st[1]);
   const double inv_max = fmax(st[0] - sqrt(st[1]), 0.00000001);
   const int res = find_epipolar_match_direct<G8>(m, a.mopt, ref, cur, T_cur_ref, a.px[2 * i], a.px[2 * i + 1], f, a.grad[2 * i],
-                                                 a.grad[2 * i + 1], a.level[i], type, st[0], inv_min, inv_max, depth);
-  if (!reporter) return;   // the lanes of a unit hold the same results: one of them reports and updates the seed
+                                                 a.grad[2 * i + 1], a.level[i], type0, st[0], inv_min, inv_max, depth);
+  if (!u.reporter) return;   // the lanes of a unit hold the same results: one of them reports and updates the seed
   if (a.result) a.result[i] = res;
   // matcher state as reprojector_utils::matchCandidate reads it after updateSeed (reprojector.cpp:403-413, 473-476)
   if (a.px_cur) { a.px_cur[2 * i] = m.px_cur[0]; a.px_cur[2 * i + 1] = m.px_cur[1]; }
@@ -2057,22 +2163,11 @@ __device__ __forceinline__ void update_seeds_body(const MatcherArgs& a, int bloc
     if (!m.reject) a.state[4 * i + 3] = st[3] + 1;  // seed::increaseOutlierProbability
     return;
   }
-  const double depth_sigma = compute_tau(inverse(T_cur_ref), f, depth, a.dopt.px_error_angle);
-  const double z = 1.0 / depth;
-  const double sg = 0.5 * (1.0 / fmax(0.000000000001, depth - depth_sigma) - 1.0 / (depth + depth_sigma));
-  const double tau2 = sg * sg;
-  bool ok;
-  if (a.dopt.use_vogiatzis_update) ok = update_filter_vogiatzis(z, tau2, ref.seed_mu_range, st);
-  else ok = update_filter_gaussian(z, tau2, st);
+  int type = type0;
+  const bool ok = seed_update_apply(a.dopt, ref, T_cur_ref, f, depth, cur_thresh, st, type);
   a.state[4 * i] = st[0]; a.state[4 * i + 1] = st[1]; a.state[4 * i + 2] = st[2]; a.state[4 * i + 3] = st[3];
-  if (!ok) { a.type[i] = SVOH_FT_OUTLIER; return; }
-  const double thresh = ref.seed_mu_range / cur_thresh;
-  if (st[1] < thresh * thresh) {
-    if (type == SVOH_FT_CORNER_SEED) a.type[i] = SVOH_FT_CORNER_SEED_CONVERGED;
-    else if (type == SVOH_FT_EDGELET_SEED) a.type[i] = SVOH_FT_EDGELET_SEED_CONVERGED;
-    else if (type == SVOH_FT_MAPPOINT_SEED) a.type[i] = SVOH_FT_MAPPOINT_SEED_CONVERGED;
-  }
-  a.success[i] = 1;
+  if (type != type0) a.type[i] = (uint8_t)type;
+  if (ok) a.success[i] = 1;
 #ifdef SVOH_SEED_STAMPS
   SVOH_MSTAMP(m, 0);
   flush_counters(a.unit_counts, i, m, 1);
@@ -2102,9 +2197,9 @@ __global__ __launch_bounds__(64) void match_mixed_kernel(const MatcherArgs ad, c
 // addKeyframe the fresh seeds are updated with the last frame and then with every overlap keyframe in turn.  Per seed that
 // is a dependent chain -- the search range of step j + 1 comes from the sigma2 step j left, and the type may change in
 // between -- and the seeds do not interact: every unit walks the frame list of its reference frame here, state and type
-// in registers, instead of one launch and one round trip per list entry.  One step is what update_seeds_body does to the
-// unit with that current frame, in the same order and with the same operations (the lanes of a unit all compute the
-// same, so every lane carries the state to the next step; one of them reports).
+// in registers, instead of one launch and one round trip per list entry.  One step is seed_update_step: what
+// update_seeds_body does to the unit with that current frame (the lanes of a unit all compute the same, so every lane
+// carries the state to the next step; one of them reports).
 struct SeedChainArgs {
   const int32_t* chain_begin;   // n_ref_frames + 1: the units of reference frame r walk chain_idx[chain_begin[r] .. chain_begin[r + 1])
   const int32_t* chain_idx;     // indices into MatcherArgs::cur_frame (n_cur_frames of them); validated by the host
@@ -2114,73 +2209,15 @@ struct SeedChainArgs {
   int max_steps;
 };
 
-// one step: returns updateSeed's return value; res = the matcher's result, or SVOH_MATCH_NOT_RUN when the step returned before it
-template <int G8>
-__device__ __forceinline__ bool update_seed_chain_step(const MatcherArgs& a, MatcherState& m, const DevFrameView& ref, const DevFrameView& cur,
-                                                       double pxr, double pyr, const Vec3& f, double gx, double gy, int level,
-                                                       double (&st)[4], int& type, int& res)
-{
-  res = SVOH_MATCH_NOT_RUN;
-  if (!(type < 6)) return false;  // isSeed
-  double cur_thresh = a.dopt.seed_convergence_sigma2_thresh;
-  if (type == SVOH_FT_MAPPOINT_SEED || type == SVOH_FT_MAPPOINT_SEED_CONVERGED)
-    cur_thresh = a.dopt.mappoint_convergence_sigma2_thresh;
-  if (cur.id == ref.id) return false;
-  if (type == SVOH_FT_OUTLIER) return false;
-  if ((type == SVOH_FT_CORNER_SEED_CONVERGED || type == SVOH_FT_EDGELET_SEED_CONVERGED ||
-       type == SVOH_FT_MAPPOINT_SEED_CONVERGED) && a.dopt.check_convergence)
-    return false;
-  const Rigid T_cur_ref = T_cur_ref_of(ref, cur);
-  if (a.dopt.check_visibility) {
-    const double depth = 1.0 / st[0];
-    const Vec3 p = { depth * f.x, depth * f.y, depth * f.z };
-    double px, py;
-    project3(cur.cam, transform(T_cur_ref, p), px, py);
-    if (!(px >= 0.0 && py >= 0.0 && px < (double)cur.cam.width && py < (double)cur.cam.height)) return false;
-    const int pxi0 = (int)px, pxi1 = (int)py;
-    const int boundary = 9;
-    if (!(pxi0 >= boundary && pxi1 >= boundary && pxi0 < cur.cam.width - boundary && pxi1 < cur.cam.height - boundary)) return false;
-  }
-  // a fresh Matcher per updateSeed, as in update_seeds_body (the work counters run on)
-  m.h_inv = 0.0; m.search_level = 0; m.reject = false;
-  m.align_1d = (type == SVOH_FT_EDGELET_SEED || type == SVOH_FT_EDGELET_SEED_CONVERGED);
-  m.A[0] = m.A[1] = m.A[2] = m.A[3] = 0.0;
-  m.px_cur[0] = m.px_cur[1] = 0.0;
-  m.f_cur = { 0.0, 0.0, 0.0 };
-  double depth = 0.0;
-  const double inv_min = st[0] + sqrt(st[1]);
-  const double inv_max = fmax(st[0] - sqrt(st[1]), 0.00000001);
-  res = find_epipolar_match_direct<G8>(m, a.mopt, ref, cur, T_cur_ref, pxr, pyr, f, gx, gy, level, type, st[0], inv_min, inv_max, depth);
-  if (res != SVOH_MATCH_SUCCESS) {
-    if (!m.reject) st[3] = st[3] + 1;  // seed::increaseOutlierProbability
-    return false;
-  }
-  const double depth_sigma = compute_tau(inverse(T_cur_ref), f, depth, a.dopt.px_error_angle);
-  const double z = 1.0 / depth;
-  const double sg = 0.5 * (1.0 / fmax(0.000000000001, depth - depth_sigma) - 1.0 / (depth + depth_sigma));
-  const double tau2 = sg * sg;
-  bool ok;
-  if (a.dopt.use_vogiatzis_update) ok = update_filter_vogiatzis(z, tau2, ref.seed_mu_range, st);
-  else ok = update_filter_gaussian(z, tau2, st);
-  if (!ok) { type = SVOH_FT_OUTLIER; return false; }
-  const double thresh = ref.seed_mu_range / cur_thresh;
-  if (st[1] < thresh * thresh) {
-    if (type == SVOH_FT_CORNER_SEED) type = SVOH_FT_CORNER_SEED_CONVERGED;
-    else if (type == SVOH_FT_EDGELET_SEED) type = SVOH_FT_EDGELET_SEED_CONVERGED;
-    else if (type == SVOH_FT_MAPPOINT_SEED) type = SVOH_FT_MAPPOINT_SEED_CONVERGED;
-  }
-  return true;
-}
-
 // G8: 0 one lane per unit, 1 eight lanes per unit, 3 one wave per unit, as update_seeds_kernel
 template <int G8>
 __global__ __launch_bounds__(64) void update_seeds_chain_kernel(const MatcherArgs a, const SeedChainArgs c)
 {
   __shared__ __attribute__((aligned(16))) unsigned char s_pwb[64 * kPwbStride];
-  const int unit = G8 == 1 ? (int)(threadIdx.x >> 3) : (G8 == 3 ? 0 : (int)threadIdx.x);
-  const int i = (int)blockIdx.x * (G8 == 1 ? 8 : (G8 == 3 ? 1 : 64)) + unit;
+  const UnitOfThread u = unit_of_thread<G8>((int)blockIdx.x);
+  const int i = u.i;
   if (i >= a.n) return;
-  const bool reporter = G8 == 0 || (G8 == 1 && (threadIdx.x & 7) == 0) || (G8 == 3 && (threadIdx.x & 63) == 0);
+  const bool reporter = u.reporter;
   // (host arrays only: reference index, level and the chains were validated before anything was staged)
   const int ri = a.ref_frame_idx[i];
   const DevFrameView& ref = a.ref_frames[ri];
@@ -2189,12 +2226,7 @@ __global__ __launch_bounds__(64) void update_seeds_chain_kernel(const MatcherArg
   int type = a.type[i];
   double st[4] = { a.state[4 * i], a.state[4 * i + 1], a.state[4 * i + 2], a.state[4 * i + 3] };
   MatcherState m;
-  m.pwb = s_pwb + unit * kPwbStride;
-  m.sub = G8 ? (int)(threadIdx.x & 7) : 0;
-  m.n_warp = 0; m.n_zmssd = 0; m.n_align_it = 0;
-#ifdef SVOH_SEED_STAMPS
-  m.t[0] = m.t[1] = m.t[2] = m.t[3] = 0; m.tlast = clock64();
-#endif
+  matcher_state_reset(m, s_pwb + u.unit * kPwbStride, G8 ? (int)(threadIdx.x & 7) : 0, false);   // the work counters run across the steps
   int n_ok = 0;
   for (int j = 0; j < len; ++j) {
     if (G8) g8_lds_fence();   // the patch of the step before has been read by every lane before this step's warp writes it
@@ -2202,7 +2234,7 @@ __global__ __launch_bounds__(64) void update_seeds_chain_kernel(const MatcherArg
     // (the unit's columns are read again at every step, as a single call reads them: seven doubles less to carry through the search)
     const Vec3 f = { a.f[3 * i], a.f[3 * i + 1], a.f[3 * i + 2] };
     int res;
-    const bool ok = update_seed_chain_step<G8>(a, m, ref, cur, a.px[2 * i], a.px[2 * i + 1], f, a.grad[2 * i], a.grad[2 * i + 1], a.level[i], st, type, res);
+    const bool ok = seed_update_step<G8>(a, m, ref, cur, a.px[2 * i], a.px[2 * i + 1], f, a.grad[2 * i], a.grad[2 * i + 1], a.level[i], st, type, res);
     n_ok += ok ? 1 : 0;
     if (reporter) {
       if (c.step_result) c.step_result[(size_t)i * c.max_steps + j] = res;
@@ -2511,58 +2543,29 @@ __global__ __launch_bounds__(kPkThreads) __attribute__((amdgpu_waves_per_eu(3)))
   if (indices_ok) {
     const DevFrameView& ref = a.ref_frames[ri];
     const DevFrameView& cur = a.cur_frame[ci];
-    bool run = type < 6 && cur.id != ref.id && type != SVOH_FT_OUTLIER;
-    if ((type == SVOH_FT_CORNER_SEED_CONVERGED || type == SVOH_FT_EDGELET_SEED_CONVERGED ||
-         type == SVOH_FT_MAPPOINT_SEED_CONVERGED) && a.dopt.check_convergence)
-      run = false;
-    if (run) {
-      double st[4];
-      load_state(st);
-      const double st0 = st[0], st1 = st[1];
+    const double* state_p = rec_in ? rec_in[slot_i].state : a.state + 4 * i;
+    const double* f_p = WS ? ws_f + 3 * ws_q : (rec_in ? rec_in[slot_i].f : a.f + 3 * i);
+    Rigid T_cur_ref;
+    if (seed_update_gate(a.dopt, ref, cur, type, state_p, f_p, T_cur_ref)) {
+      const double st0 = state_p[0], st1 = state_p[1];
       const Vec3 f = load_f();
-      const Rigid T_cur_ref = T_cur_ref_of(ref, cur);
-      if (a.dopt.check_visibility) {
-        const double depth = 1.0 / st0;
-        const Vec3 p = { depth * f.x, depth * f.y, depth * f.z };
-        double px, py;
-        project3(cur.cam, transform(T_cur_ref, p), px, py);
-        if (!(px >= 0.0 && py >= 0.0 && px < (double)cur.cam.width && py < (double)cur.cam.height)) run = false;
-        else {
-          const int pxi0 = (int)px, pxi1 = (int)py;
-          const int boundary = 9;
-          if (!(pxi0 >= boundary && pxi1 >= boundary && pxi0 < cur.cam.width - boundary && pxi1 < cur.cam.height - boundary)) run = false;
-        }
-      }
-      if (run) {
-        MatcherState m;
-        m.pwb = s_pwb + tid * kPwbStride;
-        m.sub = 0;
-        m.h_inv = 0.0; m.search_level = 0; m.reject = false;
-        m.n_warp = 0; m.n_zmssd = 0; m.n_align_it = 0;
-        m.align_1d = (type == SVOH_FT_EDGELET_SEED || type == SVOH_FT_EDGELET_SEED_CONVERGED);
-        m.A[0] = m.A[1] = m.A[2] = m.A[3] = 0.0;
-        m.px_cur[0] = m.px_cur[1] = 0.0;
-        m.f_cur = { 0.0, 0.0, 0.0 };
-        m.epi_dir[0] = m.epi_dir[1] = 0.0;
-#ifdef SVOH_SEED_STAMPS
-        m.t[0] = m.t[1] = m.t[2] = m.t[3] = 0; m.tlast = clock64();
-#endif
-        const double inv_min = st0 + sqrt(st1);
-        const double inv_max = fmax(st0 - sqrt(st1), 0.00000001);
-        code = epipolar_match_search<2>(m, a.mopt, ref, cur, T_cur_ref, pxr, pyr, f, gx, gy, level, type, st0, inv_min, inv_max);
-        search_level = m.search_level; reject = m.reject;
-        n_warp = m.n_warp; n_zmssd = m.n_zmssd;
+      MatcherState m;
+      matcher_state_reset(m, s_pwb + tid * kPwbStride, 0, type == SVOH_FT_EDGELET_SEED || type == SVOH_FT_EDGELET_SEED_CONVERGED);
+      const double inv_min = st0 + sqrt(st1);
+      const double inv_max = fmax(st0 - sqrt(st1), 0.00000001);
+      code = epipolar_match_search<2>(m, a.mopt, ref, cur, T_cur_ref, pxr, pyr, f, gx, gy, level, type, st0, inv_min, inv_max);
+      search_level = m.search_level; reject = m.reject;
+      n_warp = m.n_warp; n_zmssd = m.n_zmssd;
 #if defined(SVOH_PK_STAMPS) && defined(SVOH_SEED_STAMPS)
-        tsg[0] = m.t[0]; tsg[1] = m.t[1]; tsg[2] = m.t[2];
+      tsg[0] = m.t[0]; tsg[1] = m.t[1]; tsg[2] = m.t[2];
 #endif
-        px_cur0 = m.px_cur[0]; px_cur1 = m.px_cur[1];
-        if (a.search_level) a.search_level[i] = m.search_level;
-        if (a.A_cur_ref) for (int k = 0; k < 4; ++k) a.A_cur_ref[4 * i + k] = m.A[k];
+      px_cur0 = m.px_cur[0]; px_cur1 = m.px_cur[1];
+      if (a.search_level) a.search_level[i] = m.search_level;
+      if (a.A_cur_ref) for (int k = 0; k < 4; ++k) a.A_cur_ref[4 * i + k] = m.A[k];
 #ifdef SVOH_PK_STAMPS
-        tsA1 = clock64();
+      tsA1 = clock64();
 #endif
-        is_1d = m.align_1d; edir0 = m.epi_dir[0]; edir1 = m.epi_dir[1];
-      }
+      is_1d = m.align_1d; edir0 = m.epi_dir[0]; edir1 = m.epi_dir[1];
     }
   }
   // every lane leaves (cur frame, search level) of its slot where the lanes of a refinement job find them
@@ -2606,6 +2609,7 @@ __global__ __launch_bounds__(kPkThreads) __attribute__((amdgpu_waves_per_eu(3)))
       MatcherState m;
       m.search_level = search_level;
       m.px_cur[0] = px_cur0; m.px_cur[1] = px_cur1;
+      m.f_cur = { 0.0, 0.0, 0.0 };   // (read back below when the refinement failed: zeros, as the per-unit kernels report)
       bool aligned = false;
       double sx = 0.0, sy = 0.0;
       if (code == kMatchRefinePending) {
@@ -2626,27 +2630,8 @@ __global__ __launch_bounds__(kPkThreads) __attribute__((amdgpu_waves_per_eu(3)))
     if (res != SVOH_MATCH_SUCCESS) {
       if (!reject) { st[3] = st[3] + 1; state_changed = true; }  // seed::increaseOutlierProbability
     } else {
-      double cur_thresh = a.dopt.seed_convergence_sigma2_thresh;
-      if (type == SVOH_FT_MAPPOINT_SEED || type == SVOH_FT_MAPPOINT_SEED_CONVERGED)
-        cur_thresh = a.dopt.mappoint_convergence_sigma2_thresh;
-      const double depth_sigma = compute_tau(inverse(T_cur_ref), f, depth, a.dopt.px_error_angle);
-      const double z = 1.0 / depth;
-      const double sg = 0.5 * (1.0 / fmax(0.000000000001, depth - depth_sigma) - 1.0 / (depth + depth_sigma));
-      const double tau2 = sg * sg;
-      bool ok;
-      if (a.dopt.use_vogiatzis_update) ok = update_filter_vogiatzis(z, tau2, ref.seed_mu_range, st);
-      else ok = update_filter_gaussian(z, tau2, st);
+      out_success = seed_update_apply(a.dopt, ref, T_cur_ref, f, depth, seed_convergence_thresh(a.dopt, type), st, out_type) ? 1 : 0;
       state_changed = true;
-      if (!ok) out_type = SVOH_FT_OUTLIER;
-      else {
-        const double thresh = ref.seed_mu_range / cur_thresh;
-        if (st[1] < thresh * thresh) {
-          if (type == SVOH_FT_CORNER_SEED) out_type = SVOH_FT_CORNER_SEED_CONVERGED;
-          else if (type == SVOH_FT_EDGELET_SEED) out_type = SVOH_FT_EDGELET_SEED_CONVERGED;
-          else if (type == SVOH_FT_MAPPOINT_SEED) out_type = SVOH_FT_MAPPOINT_SEED_CONVERGED;
-        }
-        out_success = 1;
-      }
     }
   }
 #ifdef SVOH_PK_STAMPS
@@ -2680,10 +2665,10 @@ template <int G8>
 __global__ __launch_bounds__(64) void epipolar_match_kernel(const MatcherArgs a)
 {
   __shared__ __attribute__((aligned(16))) unsigned char s_pwb[64 * kPwbStride];
-  const int unit = G8 == 1 ? (int)(threadIdx.x >> 3) : (G8 == 3 ? 0 : (int)threadIdx.x);
-  const int i = blockIdx.x * (G8 == 1 ? 8 : (G8 == 3 ? 1 : 64)) + unit;
+  const UnitOfThread u = unit_of_thread<G8>((int)blockIdx.x);
+  const int i = u.i;
   if (i >= a.n) return;
-  const bool reporter = G8 == 0 || (G8 == 1 && (threadIdx.x & 7) == 0) || (G8 == 3 && (threadIdx.x & 63) == 0);
+  const bool reporter = u.reporter;
   if (!feature_indices_ok(a, i)) {
     if (reporter) {
       a.result[i] = SVOH_MATCH_NOT_RUN;
@@ -2697,17 +2682,7 @@ __global__ __launch_bounds__(64) void epipolar_match_kernel(const MatcherArgs a)
   const Rigid T_cur_ref = a.T_cur_ref ? a.T_cur_ref[(size_t)ri * a.n_cur_frames + ci] : T_cur_ref_of(ref, cur);
   const int type = a.type[i];
   MatcherState m;
-  m.pwb = s_pwb + unit * kPwbStride;
-  m.sub = G8 ? (int)(threadIdx.x & 7) : 0;
-  m.h_inv = 0.0; m.search_level = 0; m.reject = false;
-  m.n_warp = 0; m.n_zmssd = 0; m.n_align_it = 0;
-  m.align_1d = is_edgelet(type);
-  m.A[0] = m.A[1] = m.A[2] = m.A[3] = 0.0;
-  m.px_cur[0] = m.px_cur[1] = 0.0;
-  m.f_cur = { 0.0, 0.0, 0.0 };
-#ifdef SVOH_SEED_STAMPS
-  m.t[0] = m.t[1] = m.t[2] = m.t[3] = 0; m.tlast = clock64();
-#endif
+  matcher_state_reset(m, s_pwb + u.unit * kPwbStride, G8 ? (int)(threadIdx.x & 7) : 0, is_edgelet(type));
   const Vec3 f = { a.f[3 * i], a.f[3 * i + 1], a.f[3 * i + 2] };
   const double d_est = a.d_inv ? a.d_inv[3 * i] : a.d_inv_common[0];
   const double d_min = a.d_inv ? a.d_inv[3 * i + 1] : a.d_inv_common[1];
@@ -2765,18 +2740,7 @@ __global__ __launch_bounds__(kPkThreads) __attribute__((amdgpu_waves_per_eu(3)))
     const Vec3 f = { a.f[3 * i], a.f[3 * i + 1], a.f[3 * i + 2] };
     const double pxr = a.px[2 * i], pyr = a.px[2 * i + 1], gx = a.grad[2 * i], gy = a.grad[2 * i + 1];
     MatcherState m;
-    m.pwb = s_pwb + tid * kPwbStride;
-    m.sub = 0;
-    m.h_inv = 0.0; m.search_level = 0; m.reject = false;
-    m.n_warp = 0; m.n_zmssd = 0; m.n_align_it = 0;
-    m.align_1d = is_edgelet(type);
-    m.A[0] = m.A[1] = m.A[2] = m.A[3] = 0.0;
-    m.px_cur[0] = m.px_cur[1] = 0.0;
-    m.f_cur = { 0.0, 0.0, 0.0 };
-    m.epi_dir[0] = m.epi_dir[1] = 0.0;
-#ifdef SVOH_SEED_STAMPS
-    m.t[0] = m.t[1] = m.t[2] = m.t[3] = 0; m.tlast = clock64();
-#endif
+    matcher_state_reset(m, s_pwb + tid * kPwbStride, 0, is_edgelet(type));
     is_1d = m.align_1d;
     if constexpr (DIRECT) {
       // Matcher::findMatchDirect up to the refinement (matcher.cpp:31-93)

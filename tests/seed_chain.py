@@ -54,9 +54,8 @@ def make_data(cam_kind="pinhole", seed=SCENE_SEED):
     # never to convergence, and the chain has to carry a seed that converges on the way as a converged seed
     st = sd["state"].reshape(-1, 4)
     late = np.arange(3, n, 23)
-    # (corner and edgelet seeds only.  A map-point seed whose sigma2 lies between the two convergence thresholds is where
-    # the single-call per-unit kernels and the oracle disagree today -- the kernels mark it converged at the seed threshold,
-    # the oracle, the packed kernel and the chain kernel wait for the map-point threshold -- and the chain cannot equal both)
+    # (corner and edgelet seeds only: the data dates from when the single-call per-unit kernels marked a map-point seed
+    # converged at the seed threshold.  Map-point seeds between the two thresholds are tests/seed_exits.py's now.)
     late = late[late % 17 != 0]
     st[late, 0] = 1.0 / (sd["true_depth"][late] * np.random.RandomState(seed + 77).uniform(0.995, 1.005, late.size))
     st[late, 1] = (sd["mu_range"] / 199.9) ** 2

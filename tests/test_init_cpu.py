@@ -16,6 +16,12 @@ TOOL_DIR = os.path.join(ROOT, "tests", "cpp_init")
 TOOL, TOOL_SAN = os.path.join(TOOL_DIR, "init_tool"), os.path.join(TOOL_DIR, "init_tool_san")
 
 
+@pytest.fixture(scope="module", autouse=True)
+def tools():
+    """The two tools, made here when build() has not left them (they need the compiler only); nothing to do otherwise."""
+    subprocess.check_call(["make", "-s", "-C", TOOL_DIR, "init_tool", "init_tool_san"])
+
+
 # ---------------------------------------------------------------- the estimator's restatement
 def test_mix_is_splitmix64():
     # the first three outputs of splitmix64 seeded with 0 (Vigna's reference values)

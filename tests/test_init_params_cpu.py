@@ -2,8 +2,17 @@
 import os
 import subprocess
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "tests", "cpp_init", "init_params_tool")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def tool():
+    """The tool, made here when build() has not left it (it links the host library); nothing to do otherwise."""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "svo_pro_universal_amd", "host"), "libsvo_hip_host.so"])
+    subprocess.check_call(["make", "-s", "-C", os.path.dirname(TOOL), "init_params_tool"])
 
 DEFAULTS = dict(init_min_features="100", init_min_tracked="80", init_min_inliers="70", init_min_disparity="40",
                 init_min_features_factor="2", init_disparity_pivot_ratio="0.5", reproj_err_thresh="2", map_scale="1",
