@@ -1137,6 +1137,54 @@ typedef struct svoh_homography_result {
 int svoh_homography_ransac_batch(svoh_ctx* ctx, const svoh_init_options* options, int n_problems,
                                  const svoh_homography_problem* problems, svoh_homography_result* results, uint8_t* masks);
 
+/* ---- translation estimator of the mono bootstrap with a rotation prior (csrc/init.hip; DESIGN.md, "TwoPoint initialiser") ----
+ * Stands where svo::TwoPointInit runs opengv's RANSAC over TranslationSacProblemWithTriangulation
+ * (src/svo/src/initialization.cpp:167-289): opengv's sampling and early stop cannot be restated, so this is an estimator
+ * of our own whose result is a function of its inputs alone; its score is the reference's.  Per problem: n matches as
+ * unit bearing vectors (f_cur, f_ref: n x 3 doubles, host), the known rotation R_cur_ref (row-major), thresh (the
+ * reference: 1 - cos(getAngleError(reproj_error_thresh))), a 64-bit seed; all n_hypotheses hypotheses are run.
+ *   1. Staging: g_i = R_cur_ref f_ref_i, m_i = f_cur_i x g_i.  With c = f_cur.g the triangulation matrix of a match is
+ *      A = [[f_cur.f_cur, -c], [c, -g.g]], its inverse [[-g.g, c], [-c, f_cur.f_cur]] (1 / (c c - f_cur.f_cur g.g)).
+ *   2. Hypothesis h draws mix(seed ^ mix((h << 8) + d)) mod n (mix: as above) for d = 0, 1, ... < 64 until it has two
+ *      different indices (i, j).
+ *   3. t = m_i x m_j; the hypothesis is degenerate when !(|t| >= 1e-12) (a NaN, a pure rotation) or when the draws do
+ *      not yield two indices; else t /= |t|, and t = -t when (f_cur_i - g_i).t < 0.
+ *   4. Every hypothesis is scored on every match: b = (t.f_cur, t.g), lambda = A^-1 b,
+ *      p = ((lambda0 f_cur + t) + lambda1 g) / 2, q = p - t, err = (1 - f_cur.p/|p|) + (1 - g.q/|q|); an inlier iff
+ *      err < thresh (false for a NaN).  The largest count wins, the lowest h among equals.  (1/|p| and 1/|q| on the
+ *      device: the hardware's reciprocal square root and two Newton steps, a few 1e-16 from the quotient.)
+ *   5. No hypothesis that is not degenerate, or a winning count below 2 (always so for n < 2): status
+ *      SVOH_TRANSLATION_NO_MODEL and every other output zero.
+ *   6. M = sum mhat mhat^T over the winner's inliers with |m| >= 1e-12, mhat = m / |m|; t becomes the unit eigenvector of
+ *      M's smallest eigenvalue, by 8 sweeps of cyclic Jacobi over the pairs (0,1), (0,2), (1,2) (a pair whose entry is
+ *      exactly zero is passed over; rotation angle by tan = sign(theta) / (|theta| + sqrt(theta^2 + 1)),
+ *      theta = (a_qq - a_pp) / (2 a_pq)), its sign such that its dot product with the winner's t is >= 0; a result that
+ *      is not finite keeps the winner's t.
+ *   7. The mask and n_inliers are rule 4 once more with the final t.
+ * n > 1024: SVOH_ERR_INVALID_ARGUMENT, nothing written.  masks: one byte per match, the problems' one after the other.
+ * Blocking; one workgroup per problem, and a problem's result does not depend on what else is in the batch. */
+enum { SVOH_TRANSLATION_OK = 0, SVOH_TRANSLATION_NO_MODEL = 1 };
+typedef struct svoh_translation_problem {
+  int32_t n;
+  int32_t reserved;
+  const double* f_cur;            /* n x 3 */
+  const double* f_ref;            /* n x 3 */
+  double R_cur_ref[9];            /* row-major */
+  double thresh;
+  uint64_t seed;
+} svoh_translation_problem;
+typedef struct svoh_translation_result {
+  double t[3];                    /* unit: the direction of t_cur_ref */
+  int32_t best_hypothesis;
+  int32_t n_inliers_hypothesis;   /* the winner's count, before the refinement */
+  int32_t n_inliers;              /* after it: the number of ones in the mask */
+  int32_t n_degenerate;           /* hypotheses without a model */
+  int32_t status;                 /* SVOH_TRANSLATION_* */
+  int32_t reserved;
+} svoh_translation_result;
+int svoh_translation_ransac_batch(svoh_ctx* ctx, const svoh_init_options* options, int n_problems,
+                                  const svoh_translation_problem* problems, svoh_translation_result* results, uint8_t* masks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -222,8 +222,22 @@ class svoh_homography_result(C.Structure):
                 ("n_inliers", C.c_int32), ("refine_iters", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+SVOH_TRANSLATION_OK, SVOH_TRANSLATION_NO_MODEL = 0, 1
+
+
+class svoh_translation_problem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("f_cur", C.c_void_p), ("f_ref", C.c_void_p),
+                ("R_cur_ref", C.c_double * 9), ("thresh", C.c_double), ("seed", C.c_uint64)]
+
+
+class svoh_translation_result(C.Structure):
+    _fields_ = [("t", C.c_double * 3), ("best_hypothesis", C.c_int32), ("n_inliers_hypothesis", C.c_int32),
+                ("n_inliers", C.c_int32), ("n_degenerate", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 def default_init_options(**kw):
-    """The homography initialiser's estimator (include/svo_hip.h, svoh_homography_ransac_batch): 2000 hypotheses."""
+    """The initialisers' estimators (include/svo_hip.h, svoh_homography_ransac_batch, svoh_translation_ransac_batch):
+    2000 hypotheses."""
     o = svoh_init_options(n_hypotheses=2000)
     for k, v in kw.items():
         if not hasattr(o, k):
@@ -339,6 +353,8 @@ EXPORTS = [
     "svoh_mask_upload", "svoh_mask_release", "svoh_detect_cells_batch_masked", "svoh_detect_cells_batch_masked_enqueue",
     # mono bootstrap: the homography estimator (csrc/init.hip)
     "svoh_homography_ransac_batch",
+    # ... and the translation estimator under a known rotation (the TwoPoint initialiser)
+    "svoh_translation_ransac_batch",
 ]
 
 
@@ -489,6 +505,8 @@ def load(path=None):
     lib.svoh_detect_cells_batch_masked_enqueue.argtypes = [C.c_void_p, C.c_int, P(svoh_frame_t), P(svoh_detector_options), C.c_void_p, P(svoh_mask_t)]
     lib.svoh_homography_ransac_batch.argtypes = [C.c_void_p, P(svoh_init_options), C.c_int, P(svoh_homography_problem),
                                                  P(svoh_homography_result), C.c_void_p]
+    lib.svoh_translation_ransac_batch.argtypes = [C.c_void_p, P(svoh_init_options), C.c_int, P(svoh_translation_problem),
+                                                  P(svoh_translation_result), C.c_void_p]
     lib.svoh_histogram_angle_bins.argtypes = [C.c_void_p, C.c_int, P(svoh_frame_t), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.svoh_detect_fill_features.argtypes = [P(svoh_detector_options), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int32)]

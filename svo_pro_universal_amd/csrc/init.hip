@@ -1,5 +1,6 @@
-// init.hip -- the homography estimator of the mono bootstrap ("Homography initialiser"): a batch of
-// RANSAC problems, one workgroup of 256 threads per problem.
+// init.hip -- the estimators of the mono bootstrap, each a batch of RANSAC problems with one workgroup of 256 threads per
+// problem: the homography ("Homography initialiser"; below) and the translation under a known rotation
+// ("TwoPoint initialiser"; translation_ransac_kernel, in the file's second half).
 //
 // The reference calls cv::findHomography(..., cv::RANSAC, thresh) (vikit_common/src/homography.cpp:36-43), whose random
 // numbers, early stop and polish are OpenCV's.  This is an estimator of our own, a function of its inputs alone:
@@ -20,6 +21,7 @@
 
 #include "svoh_internal.h"
 #include "svoh_device_utils.h"
+#include "svoh_translation.h"
 
 namespace svoh {
 
@@ -327,6 +329,173 @@ __global__ __launch_bounds__(kInitThreads) void homography_ransac_kernel(const I
   }
 }
 
+// ---- the translation estimator (include/svo_hip.h, svoh_translation_ransac_batch) ----------------------------------------
+// The reference's TwoPointInit runs OpenGV's RANSAC over TranslationSacProblemWithTriangulation (initialization.cpp:167-289);
+// its sampling and early stop are OpenGV's, so the estimator is our own and deterministic, with the reference's score:
+//   1. a match is staged as f_cur, g = R_cur_ref f_ref and the inverse of its 2x2 triangulation matrix (nine columns in LDS);
+//   2. hypothesis h draws two different matches from the counter-based generator;
+//   3. t = m_i x m_j, m = f_cur x g, normalised, pointing from where the ray was to where it is;
+//   4. every hypothesis is scored on every match (translation_count_inliers: a model in, its count out);
+//   5. the winner's inliers give M = sum mhat mhat^T, the refined t is the eigenvector of its smallest eigenvalue;
+//   6. the mask and the count with the refined t.
+// The per-hypothesis maths is svoh_translation.h's, shared with the host.
+namespace {
+
+struct TranslationProblemDev {
+  double R[9];
+  double thresh;
+  unsigned long long seed;
+  int32_t n;
+  int32_t first;        // the problem's first match in the mask array; its bearings start at double 6 * first
+};
+
+struct TranslationArgs {
+  const TranslationProblemDev* problems;
+  const double* bearings;         // per problem: f_cur[3 n], f_ref[3 n]
+  svoh_translation_result* results;
+  uint8_t* masks;
+  int32_t n_hypotheses;
+  int32_t lds_matches;            // capacity of the LDS columns (even, >= every n of the launch)
+};
+
+}  // namespace
+
+__global__ __launch_bounds__(kInitThreads) void translation_ransac_kernel(const TranslationArgs a)
+{
+  extern __shared__ __attribute__((aligned(16))) double s_cols[];   // kTranslationCols x lds_matches
+  __shared__ unsigned long long s_key[kInitWaves];
+  __shared__ double s_t[3];
+  __shared__ double s_red[kInitWaves][6];
+  __shared__ int s_cnt[kInitWaves], s_deg[kInitWaves];
+
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const TranslationProblemDev* pb = a.problems + blockIdx.x;
+  const int n = pb->n;
+  const int cap = a.lds_matches;
+  const double thresh = pb->thresh;
+  const unsigned long long seed = pb->seed;
+  svoh_translation_result* res = a.results + blockIdx.x;
+  uint8_t* mask = a.masks + pb->first;
+
+  {
+    double R[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = pb->R[k];
+    const double* fc = a.bearings + 6 * (size_t)pb->first;
+    const double* fr = fc + 3 * (size_t)n;
+    for (int i = tid; i < n; i += kInitThreads) {
+      const double f_cur[3] = { fc[3 * i], fc[3 * i + 1], fc[3 * i + 2] }, f_ref[3] = { fr[3 * i], fr[3 * i + 1], fr[3 * i + 2] };
+      double col[kTranslationCols];
+      translation_stage(R, f_cur, f_ref, col);
+#pragma unroll
+      for (int k = 0; k < kTranslationCols; ++k) s_cols[k * cap + i] = col[k];
+    }
+  }
+  __syncthreads();
+
+  // ---- hypotheses: thread t takes t, t + 256, ... ----
+  unsigned long long best_key = 0;   // (count + 1) << 32 | ~h: larger count first, then lower h; 0 = no model
+  double best_t[3] = { 0, 0, 0 };
+  int n_degenerate = 0;
+  if (n >= 2) {
+    for (int h = tid; h < a.n_hypotheses; h += kInitThreads) {
+      unsigned i, j;
+      double t[3];
+      bool ok = translation_sample(seed, (unsigned)h, (unsigned)n, i, j);
+      if (ok) {
+        const double fi[3] = { s_cols[i], s_cols[cap + i], s_cols[2 * cap + i] }, gi[3] = { s_cols[3 * cap + i], s_cols[4 * cap + i], s_cols[5 * cap + i] };
+        const double fj[3] = { s_cols[j], s_cols[cap + j], s_cols[2 * cap + j] }, gj[3] = { s_cols[3 * cap + j], s_cols[4 * cap + j], s_cols[5 * cap + j] };
+        ok = translation_from_two(fi, gi, fj, gj, t);
+      }
+      if (!ok) { ++n_degenerate; continue; }
+      const int count = translation_count_inliers(t, s_cols, cap, n, thresh);   // the same address for all lanes: an LDS broadcast
+      const unsigned long long key = ((unsigned long long)(unsigned)(count + 1) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)h);
+      if (key > best_key) {
+        best_key = key;
+        best_t[0] = t[0]; best_t[1] = t[1]; best_t[2] = t[2];
+      }
+    }
+  }
+
+  // ---- argmax over (count, lowest h) and the number of degenerate hypotheses ----
+  unsigned long long wkey = best_key;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const unsigned long long o = __shfl_xor(wkey, off, 64);
+    wkey = o > wkey ? o : wkey;
+  }
+  n_degenerate = wave_sum_i32_dpp(n_degenerate);
+  if (lane == 0) { s_key[wave] = wkey; s_deg[wave] = n_degenerate; }
+  __syncthreads();
+  unsigned long long gkey = s_key[0];
+#pragma unroll
+  for (int w = 1; w < kInitWaves; ++w) gkey = s_key[w] > gkey ? s_key[w] : gkey;
+  const int best_count = (int)(unsigned)(gkey >> 32) - 1;
+  const int best_h = (int)(0xFFFFFFFFu - (unsigned)gkey);
+  if (gkey == 0 || best_count < 2) {   // SVOH_TRANSLATION_NO_MODEL: every output zero
+    if (tid == 0) {
+      res->t[0] = res->t[1] = res->t[2] = 0.0;
+      res->best_hypothesis = 0; res->n_inliers_hypothesis = 0; res->n_inliers = 0; res->n_degenerate = 0;
+      res->status = SVOH_TRANSLATION_NO_MODEL; res->reserved = 0;
+    }
+    for (int i = tid; i < n; i += kInitThreads) mask[i] = 0;
+    return;
+  }
+  if (best_key == gkey) {   // keys are unique: h is part of them
+    s_t[0] = best_t[0]; s_t[1] = best_t[1]; s_t[2] = best_t[2];
+  }
+  __syncthreads();
+
+  // ---- refinement on the winner's inliers ----
+  const double t0[3] = { s_t[0], s_t[1], s_t[2] };
+  double acc[6] = { 0, 0, 0, 0, 0, 0 };
+#pragma unroll
+  for (int k = 0; k < kInitMaxMatches / kInitThreads; ++k) {
+    const int i = tid + k * kInitThreads;
+    if (i < n && translation_is_inlier(t0, s_cols, cap, i, thresh)) translation_accumulate(s_cols, cap, i, acc);
+  }
+  {
+    int ridx;
+    bool rvalid;
+    wave_reduce_scatter<6>(acc, lane, ridx, rvalid);
+    if (rvalid) s_red[wave][ridx] = acc[0];
+  }
+  __syncthreads();   // (every thread has read the winner's t before it is replaced)
+  if (tid == 0) {
+    double M[6], t[3];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) M[k] = (s_red[0][k] + s_red[1][k]) + (s_red[2][k] + s_red[3][k]);
+    translation_refine(M, t0, t);
+    s_t[0] = t[0]; s_t[1] = t[1]; s_t[2] = t[2];
+  }
+  __syncthreads();
+
+  // ---- final mask and count with the refined t ----
+  const double t[3] = { s_t[0], s_t[1], s_t[2] };
+  int count = 0;
+#pragma unroll
+  for (int k = 0; k < kInitMaxMatches / kInitThreads; ++k) {
+    const int i = tid + k * kInitThreads;
+    if (i < n) {
+      const bool in = translation_is_inlier(t, s_cols, cap, i, thresh);
+      mask[i] = in ? 1 : 0;
+      count += in ? 1 : 0;
+    }
+  }
+  count = wave_sum_i32_dpp(count);
+  if (lane == 0) s_cnt[wave] = count;
+  __syncthreads();
+  if (tid == 0) {
+    res->t[0] = t[0]; res->t[1] = t[1]; res->t[2] = t[2];
+    res->best_hypothesis = best_h;
+    res->n_inliers_hypothesis = best_count;
+    res->n_inliers = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+    res->n_degenerate = (s_deg[0] + s_deg[1]) + (s_deg[2] + s_deg[3]);
+    res->status = SVOH_TRANSLATION_OK;
+    res->reserved = 0;
+  }
+}
+
 }  // namespace svoh
 
 using namespace svoh;
@@ -395,6 +564,76 @@ try {
   SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, h + o_res, d + o_res, bytes - o_res));
   SVOH_HIP_TRY(ctx, hipStreamSynchronize(stream));
   memcpy(results, h + o_res, sizeof(svoh_homography_result) * (size_t)n_problems);
+  if (total) memcpy(masks, h + o_mask, total);
+  return SVOH_OK;
+} SVOH_ABI_CATCH(ctx)
+
+extern "C" int svoh_translation_ransac_batch(svoh_ctx* ctx, const svoh_init_options* options, int n_problems,
+                                             const svoh_translation_problem* problems, svoh_translation_result* results, uint8_t* masks)
+try {
+  if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  SVOH_REQUIRE(ctx, options != nullptr, "NULL argument");
+  SVOH_REQUIRE(ctx, n_problems >= 0, "negative count");
+  SVOH_REQUIRE(ctx, options->n_hypotheses >= 0 && options->n_hypotheses <= (1 << 24), "n_hypotheses out of range (0 .. 2^24)");
+  if (n_problems == 0) return SVOH_OK;
+  SVOH_REQUIRE(ctx, problems && results, "NULL argument");
+  size_t total = 0;
+  int max_n = 0;
+  for (int p = 0; p < n_problems; ++p) {
+    const svoh_translation_problem& pb = problems[p];
+    SVOH_REQUIRE(ctx, pb.n >= 0 && pb.n <= kInitMaxMatches, "a translation problem has more than 1024 matches (or a negative count)");
+    SVOH_REQUIRE(ctx, pb.n == 0 || (pb.f_cur && pb.f_ref), "NULL bearing array");
+    total += (size_t)pb.n;
+    max_n = std::max(max_n, pb.n);
+  }
+  SVOH_REQUIRE(ctx, total == 0 || masks, "NULL mask array");
+  SVOH_REQUIRE(ctx, total <= (size_t)1 << 30, "too many matches in one call");
+  SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
+  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+  const size_t o_pb = 0, o_f = al(sizeof(TranslationProblemDev) * (size_t)n_problems);
+  const size_t o_res = o_f + al(48 * (total ? total : 1));
+  const size_t o_mask = o_res + al(sizeof(svoh_translation_result) * (size_t)n_problems);
+  const size_t bytes = o_mask + al(total ? total : 1);
+  SVOH_HIP_TRY(ctx, ctx->h_scratch0.reserve(bytes));
+  SVOH_HIP_TRY(ctx, ctx->d_scratch0.reserve(bytes));
+  uint8_t* h = static_cast<uint8_t*>(ctx->h_scratch0.ptr);
+  uint8_t* d = static_cast<uint8_t*>(ctx->d_scratch0.ptr);
+  TranslationProblemDev* hp = reinterpret_cast<TranslationProblemDev*>(h + o_pb);
+  double* hf = reinterpret_cast<double*>(h + o_f);
+  size_t first = 0;
+  for (int p = 0; p < n_problems; ++p) {
+    const svoh_translation_problem& pb = problems[p];
+    memcpy(hp[p].R, pb.R_cur_ref, sizeof hp[p].R);
+    hp[p].thresh = pb.thresh; hp[p].seed = pb.seed; hp[p].n = pb.n; hp[p].first = (int32_t)first;
+    const size_t n = (size_t)pb.n;
+    if (n) {
+      memcpy(hf + 6 * first, pb.f_cur, 3 * n * sizeof(double));
+      memcpy(hf + 6 * first + 3 * n, pb.f_ref, 3 * n * sizeof(double));
+    }
+    first += n;
+  }
+  SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d, h, o_res));
+  TranslationArgs a;
+  a.problems = reinterpret_cast<const TranslationProblemDev*>(d + o_pb);
+  a.bearings = reinterpret_cast<const double*>(d + o_f);
+  a.results = reinterpret_cast<svoh_translation_result*>(d + o_res);
+  a.masks = d + o_mask;
+  a.n_hypotheses = options->n_hypotheses;
+  a.lds_matches = std::max(2, (max_n + 1) & ~1);
+  const size_t lds = kTranslationCols * sizeof(double) * (size_t)a.lds_matches;   // 72 KB at 1024 matches
+  if (lds > 48 * 1024)
+    SVOH_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(translation_ransac_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipStream_t stream = ctx->stream;
+  const bool timed = ctx->timing_on();
+  if (timed) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_start, stream));
+  hipLaunchKernelGGL(translation_ransac_kernel, dim3((unsigned)n_problems), dim3(kInitThreads), lds, stream, a);
+  SVOH_HIP_TRY(ctx, hipGetLastError());
+  if (timed) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_stop, stream));
+  ctx->misc_timed = timed; ctx->misc_launched = true;
+  SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, h + o_res, d + o_res, bytes - o_res));
+  SVOH_HIP_TRY(ctx, hipStreamSynchronize(stream));
+  memcpy(results, h + o_res, sizeof(svoh_translation_result) * (size_t)n_problems);
   if (total) memcpy(masks, h + o_mask, total);
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)

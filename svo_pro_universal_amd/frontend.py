@@ -581,6 +581,34 @@ def _homography_ransac(self, problems, options=None):
     return [res[i] for i in range(n_pb)], [masks[off[i]:off[i + 1]].copy() for i in range(n_pb)]
 
 
+def _translation_ransac(self, problems, options=None):
+    """svoh_translation_ransac_batch: the translation estimator of the mono bootstrap with a rotation prior (the TwoPoint
+    initialiser) for a batch of problems.
+    problems: list of (f_cur [n,3], f_ref [n,3], R_cur_ref [3,3], thresh, seed) -- unit bearing vectors,
+    thresh = 1 - cos(angle error).  Returns (results: list of svoh_translation_result, masks: list of uint8 arrays [n])."""
+    opt = options if options is not None else capi.default_init_options()
+    n_pb = len(problems)
+    pbs = (capi.svoh_translation_problem * max(1, n_pb))()
+    res = (capi.svoh_translation_result * max(1, n_pb))()
+    keep, sizes = [], []
+    for i, (f_cur, f_ref, R_cur_ref, thresh, seed) in enumerate(problems):
+        a = np.ascontiguousarray(f_cur, dtype=np.float64).reshape(-1, 3)
+        b = np.ascontiguousarray(f_ref, dtype=np.float64).reshape(-1, 3)
+        if a.shape != b.shape:
+            raise ValueError("f_cur and f_ref differ in size")
+        R = np.ascontiguousarray(R_cur_ref, dtype=np.float64).reshape(9)
+        keep += [a, b]
+        sizes.append(a.shape[0])
+        pbs[i].n = a.shape[0]
+        pbs[i].f_cur, pbs[i].f_ref = a.ctypes.data, b.ctypes.data
+        pbs[i].R_cur_ref = (C.c_double * 9)(*R)
+        pbs[i].thresh, pbs[i].seed = float(thresh), int(seed) & 0xFFFFFFFFFFFFFFFF
+    masks = np.zeros(max(1, sum(sizes)), np.uint8)
+    self._check(self.lib.svoh_translation_ransac_batch(self.h, C.byref(opt), n_pb, pbs, res, masks.ctypes.data))
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+    return [res[i] for i in range(n_pb)], [masks[off[i]:off[i + 1]].copy() for i in range(n_pb)]
+
+
 def _detect_features(self, opt, frame, width, height, occupancy=None, mask=None, max_n_features=None):
     """svoh_detect_features: dict(px [n,2], score, level, grad [n,2], type) like FastGradDetector::detect."""
     n_cells = int(np.ceil(width / opt.cell_size)) * int(np.ceil(height / opt.cell_size))
@@ -676,6 +704,7 @@ Context.detect_features = _detect_features
 Context.optimize_pose = _optimize_pose
 Context.optimize_points = _optimize_points
 Context.homography_ransac = _homography_ransac
+Context.translation_ransac = _translation_ransac
 Context.klt_track_batch = _klt_track_batch
 Context.klt_track_indexed = _klt_track_indexed
 Context.update_seeds_device = _update_seeds_device

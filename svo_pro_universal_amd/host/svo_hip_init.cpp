@@ -393,6 +393,32 @@ Homography estimateHomography(svoh_ctx* ctx, const std::vector<double>& f_cur, c
 
 }  // namespace vk
 
+size_t estimateTranslation(svoh_ctx* ctx, const std::vector<double>& f_cur, const std::vector<double>& f_ref, const double R_cur_ref[9], double thresh,
+                           uint64_t seed, int n_hypotheses, double t_cur_ref[3], std::vector<uint8_t>* inliers, svoh_translation_result* result,
+                           double* ms_kernel)
+{
+  if (f_cur.size() != f_ref.size() || f_cur.size() % 3 != 0) throw std::runtime_error("estimateTranslation: f_cur and f_ref differ in size");
+  const size_t N = f_cur.size() / 3;
+  if (N > 1024) throw std::runtime_error("estimateTranslation: more than 1024 matches (svoh_translation_ransac_batch's limit)");
+  svoh_init_options opt{};
+  opt.n_hypotheses = n_hypotheses;
+  svoh_translation_problem pb{};
+  pb.n = (int32_t)N; pb.f_cur = f_cur.data(); pb.f_ref = f_ref.data(); pb.thresh = thresh; pb.seed = seed;
+  for (int i = 0; i < 9; ++i) pb.R_cur_ref[i] = R_cur_ref[i];
+  svoh_translation_result res{};
+  std::vector<uint8_t> mask(N ? N : 1, 0);
+  if (svoh_translation_ransac_batch(ctx, &opt, 1, &pb, &res, mask.data()) != SVOH_OK)
+    throw std::runtime_error(std::string("svoh_translation_ransac_batch: ") + svoh_last_error_string(ctx));
+  if (result) *result = res;
+  if (ms_kernel) {
+    float ms = -1.0f;
+    *ms_kernel = svoh_last_kernel_ms(ctx, &ms) == SVOH_OK ? (double)ms : -1.0;
+  }
+  for (int i = 0; i < 3; ++i) t_cur_ref[i] = res.t[i];   // zero without a model
+  if (inliers) { mask.resize(N); inliers->swap(mask); }
+  return res.status == SVOH_TRANSLATION_OK ? (size_t)res.n_inliers : 0;
+}
+
 namespace initialization_utils {
 
 void triangulatePoints(const Frame& frame_cur, const Frame& frame_ref, const Transformation& T_cur_ref, double reprojection_threshold,
@@ -519,18 +545,19 @@ FrameBundle::Ptr FeatureTrackerHip::getOldestFrameInTrack(size_t frame_index) co
   return active_tracks_[frame_index].front().at(0).getFrameBundle();
 }
 
-// ---- HomographyInit ---------------------------------------------------------------------------------------------------
-HomographyInitHip::HomographyInitHip(svoh_ctx* ctx, const InitializationOptions& init_options, const FeatureTrackerOptions& tracker_options,
-                                     const std::shared_ptr<DetectorHip>& detector)
+// ---- AbstractInitialization -------------------------------------------------------------------------------------------
+AbstractInitializationHip::AbstractInitializationHip(svoh_ctx* ctx, const InitializationOptions& init_options, const FeatureTrackerOptions& tracker_options,
+                                                     const std::shared_ptr<DetectorHip>& detector, const char* who)
     : ctx_(ctx), options_(init_options), tracker_(ctx, tracker_options, 1)
 {
-  if (!ctx_) throw std::runtime_error("HomographyInitHip: NULL svoh_ctx (no CPU fallback exists)");
+  if (!ctx_) throw std::runtime_error(std::string(who) + ": NULL svoh_ctx (no CPU fallback exists)");
   tracker_.setDetectors({ detector });
 }
 
-void HomographyInitHip::reset()
+void AbstractInitializationHip::reset()
 {
   frames_ref_.reset();
+  have_rotation_prior_ = false;
   have_depth_prior_ = false;
   tracker_.reset();
 }
@@ -545,7 +572,7 @@ void clearFeatureStorage(Frame& frame)
 }
 }  // namespace
 
-bool HomographyInitHip::trackFeaturesAndCheckDisparity(const FrameBundle::Ptr& frames)
+bool AbstractInitializationHip::trackFeaturesAndCheckDisparity(const FrameBundle::Ptr& frames)
 {
   tracker_.trackFrameBundle(frames);
   std::vector<size_t> num_tracked;
@@ -563,10 +590,18 @@ bool HomographyInitHip::trackFeaturesAndCheckDisparity(const FrameBundle::Ptr& f
     for (const FramePtr& frame : frames->frames_) clearFeatureStorage(*frame);
     tracker_.initializeNewTracks(frames);
     frames_ref_ = frames;
+    R_ref_world_ = R_cur_world_;
     return false;
   }
   if (avg_disparity < options_.init_min_disparity) return false;
   return true;
+}
+
+// ---- HomographyInit ---------------------------------------------------------------------------------------------------
+HomographyInitHip::HomographyInitHip(svoh_ctx* ctx, const InitializationOptions& init_options, const FeatureTrackerOptions& tracker_options,
+                                     const std::shared_ptr<DetectorHip>& detector)
+    : AbstractInitializationHip(ctx, init_options, tracker_options, detector, "HomographyInitHip")
+{
 }
 
 InitResult HomographyInitHip::addFrameBundle(const FrameBundle::Ptr& frames_cur)
@@ -612,6 +647,56 @@ InitResult HomographyInitHip::addFrameBundle(const FrameBundle::Ptr& frames_cur)
   tracker_.reset();
   clearFeatureStorage(*frames_cur->at(0));
   return InitResult::kTracking;
+}
+
+// ---- TwoPointInit -----------------------------------------------------------------------------------------------------
+TwoPointInitHip::TwoPointInitHip(svoh_ctx* ctx, const InitializationOptions& init_options, const FeatureTrackerOptions& tracker_options,
+                                 const std::shared_ptr<DetectorHip>& detector)
+    : AbstractInitializationHip(ctx, init_options, tracker_options, detector, "TwoPointInitHip")
+{
+}
+
+InitResult TwoPointInitHip::addFrameBundle(const FrameBundle::Ptr& frames_cur)
+{
+  stats_ = Statistics();
+  if (!have_rotation_prior_) return InitResult::kFailure;   // ("TwoPointInit has no rotation prior.")
+  have_rotation_prior_ = false;
+  if (!frames_cur || frames_cur->size() != 1) throw std::runtime_error("TwoPointInitHip: one camera per bundle");
+  if (!trackFeaturesAndCheckDisparity(frames_cur)) return InitResult::kTracking;
+
+  const FrameBundle::Ptr frames_ref = tracker_.getOldestFrameInTrack(0);
+  const Frame& frame_ref = *frames_ref->at(0);
+  const Frame& frame_cur = *frames_cur->at(0);
+  initialization_utils::FeatureMatches matches_cur_ref;
+  feature_tracking_utils::getFeatureMatches(frame_cur.track_id_vec_.data(), frame_cur.num_features_, frame_ref.track_id_vec_.data(), frame_ref.num_features_, &matches_cur_ref);
+  const size_t n = matches_cur_ref.size();
+  std::vector<double> f_cur(3 * n), f_ref(3 * n);   // initialization_utils::copyBearingVectors
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < 3; ++k) {
+      f_cur[3 * i + k] = frame_cur.f_vec_[3 * matches_cur_ref[i].first + k];
+      f_ref[3 * i + k] = frame_ref.f_vec_[3 * matches_cur_ref[i].second + k];
+    }
+
+  // the model: 1 - cos(Frame::getAngleError(reproj_error_thresh)) (pinhole_projection.hpp:72-76), R_cur_ref from the two priors
+  const double angle_error = std::atan(options_.reproj_error_thresh / (2.0 * frame_cur.cam.fx)) + std::atan(options_.reproj_error_thresh / (2.0 * frame_cur.cam.fy));
+  const double inlier_threshold = 1.0 - std::cos(angle_error);
+  const svoh::Quat q_cur_ref = svoh::normalized(svoh::mul(R_cur_world_, svoh::Quat{ R_ref_world_.w, -R_ref_world_.x, -R_ref_world_.y, -R_ref_world_.z }));
+  double R_cur_ref[9], t[3];
+  svoh::to_matrix(q_cur_ref, R_cur_ref);
+  double ms = -1.0;
+  const size_t n_inliers = estimateTranslation(ctx_, f_cur, f_ref, R_cur_ref, inlier_threshold, options_.seed, options_.n_hypotheses, t, nullptr, nullptr, &ms);
+  stats_.ms_ransac = ms;
+  stats_.n_inliers = n_inliers;
+  if (n_inliers < options_.init_min_inliers) return InitResult::kNoKeyframe;
+  T_cur_from_ref_ = Transformation{ q_cur_ref, svoh::Vec3{ t[0], t[1], t[2] } };
+
+  double scale = 0.0;
+  const bool ok = initialization_utils::triangulateAndInitializePoints(frames_cur->at(0), frames_ref->at(0), T_cur_from_ref_, options_.reproj_error_thresh,
+                                                                       depth_at_current_frame_, options_.init_min_inliers, matches_cur_ref, &scale);
+  stats_.n_triangulated = matches_cur_ref.size();
+  if (!ok) return InitResult::kFailure;
+  stats_.scale = scale;
+  return InitResult::kSuccess;
 }
 
 #endif  // SVOH_INIT_MATH_ONLY

@@ -1,6 +1,7 @@
 // svo_hip_init.h -- the mono bootstrap: what FrameHandlerMono::processFirstFrame runs before there is a map
 // ("Homography initialiser").  Counterparts in the reference:
 //   svo::HomographyInit::addFrameBundle            src/svo/src/initialization.cpp:86-161
+//   svo::TwoPointInit::addFrameBundle              src/svo/src/initialization.cpp:164-289
 //   vk::estimateHomography                          src/vikit/vikit_common/src/homography.cpp:19-136
 //   HomographyDecomp::removeScale, HomographyDecompInria::decompose
 //                                                   src/vikit/vikit_common/include/vikit/homography_decomp.h:121-126, 283-430
@@ -13,7 +14,7 @@
 //
 // The maths of this file makes no device call and needs nothing but this header and svoh_math.h: a CPU program compiles
 // svo_hip_init.cpp with -DSVOH_INIT_MATH_ONLY and links nothing else (tests/cpp_init).  What runs on the device
-// (estimateHomography, HomographyInitHip) is left out of such a build.
+// (estimateHomography, estimateTranslation, HomographyInitHip, TwoPointInitHip) is left out of such a build.
 #pragma once
 
 #include <cstddef>
@@ -95,6 +96,15 @@ Homography estimateHomography(svoh_ctx* ctx, const std::vector<double>& f_cur, c
                               svoh_homography_result* result = nullptr, double* ms_kernel = nullptr);
 }  // namespace vk
 
+// The model of TwoPointInit (initialization.cpp:244-266) with svoh_translation_ransac_batch where the reference runs
+// opengv's RANSAC: the unit translation t_cur_ref under the known R_cur_ref (row-major) from unit bearing vectors
+// (3 doubles a match), thresh = 1 - cos(angle error), n_hypotheses hypotheses from `seed`.  Returns the number of
+// inliers (0: no model; t is then zero); inliers (may be NULL): one flag per match.  More than 1024 matches:
+// std::runtime_error.  ms_kernel (may be NULL): the kernel's device time when kernel timing is on, else -1.
+size_t estimateTranslation(svoh_ctx* ctx, const std::vector<double>& f_cur, const std::vector<double>& f_ref, const double R_cur_ref[9],
+                           double thresh, uint64_t seed, int n_hypotheses, double t_cur_ref[3], std::vector<uint8_t>* inliers = nullptr,
+                           svoh_translation_result* result = nullptr, double* ms_kernel = nullptr);
+
 namespace initialization_utils {
 // the Frame forms (initialization.cpp:729-840): landmarks are made and hung on both frames, the current frame gets its pose
 void triangulatePoints(const Frame& frame_cur, const Frame& frame_ref, const Transformation& T_cur_ref, double reprojection_threshold,
@@ -128,30 +138,62 @@ struct InitializationOptions {
   uint64_t seed = 12345;                   // ... and its seed: the same frames give the same map
 };
 
-// svo::HomographyInit (initialization.h, initialization.cpp:86-161) on one camera.
-// Deviations: (1) the estimator (above); (2) a decomposition without four motions is a failure, not an abort; (3) kFailure
-// resets the initialiser -- the caller goes on with the next frame, where processFirstFrame falls through to its keyframe
-// code; (4) a failed triangulation restarts and returns kTracking, as the reference does.
-class HomographyInitHip {
+// What the reference's initialisers share (AbstractInitialization, initialization.h; initialization.cpp:76-113): the tracker,
+// the reference bundle, the priors, and the step every one of them starts with.
+class AbstractInitializationHip {
  public:
-  HomographyInitHip(svoh_ctx* ctx, const InitializationOptions& init_options, const FeatureTrackerOptions& tracker_options,
-                    const std::shared_ptr<DetectorHip>& detector);
-  InitResult addFrameBundle(const FrameBundle::Ptr& frames_cur);
+  AbstractInitializationHip(svoh_ctx* ctx, const InitializationOptions& init_options, const FeatureTrackerOptions& tracker_options,
+                            const std::shared_ptr<DetectorHip>& detector, const char* who);
+  virtual ~AbstractInitializationHip() = default;
+  virtual InitResult addFrameBundle(const FrameBundle::Ptr& frames_cur) = 0;
   void setDepthPrior(double depth) { depth_at_current_frame_ = depth; have_depth_prior_ = true; }
+  // R_cam_world of the frame the next addFrameBundle gets (initialization.h: setAbsoluteOrientationPrior)
+  void setAbsoluteOrientationPrior(const svoh::Quat& R_cam_world) { R_cur_world_ = R_cam_world; have_rotation_prior_ = true; }
   void reset();
   bool have_depth_prior_ = false;
   double depth_at_current_frame_ = 1.0;
+  bool have_rotation_prior_ = false;
+  svoh::Quat R_ref_world_{ 1, 0, 0, 0 }, R_cur_world_{ 1, 0, 0, 0 };
   FrameBundle::Ptr frames_ref_;
   Transformation T_cur_from_ref_{ { 1, 0, 0, 0 }, { 0, 0, 0 } };
   // of the last addFrameBundle
   struct Statistics { size_t n_tracked = 0; double disparity = 0.0; size_t n_inliers = 0, n_triangulated = 0; double scale = 0.0, ms_ransac = 0.0; } stats_;
   FeatureTrackerHip& tracker() { return tracker_; }
 
- private:
+ protected:
+  // initialization.cpp:86-113: false = keep tracking (too few tracks: they are started again from this bundle, which becomes
+  // the reference, R_ref_world_ = R_cur_world_; or too little disparity)
   bool trackFeaturesAndCheckDisparity(const FrameBundle::Ptr& frames);
   svoh_ctx* ctx_;
   InitializationOptions options_;
   FeatureTrackerHip tracker_;
+};
+
+// svo::HomographyInit (initialization.h, initialization.cpp:115-161) on one camera.
+// Deviations: (1) the estimator (above); (2) a decomposition without four motions is a failure, not an abort; (3) kFailure
+// resets the initialiser -- the caller goes on with the next frame, where processFirstFrame falls through to its keyframe
+// code; (4) a failed triangulation restarts and returns kTracking, as the reference does.
+class HomographyInitHip : public AbstractInitializationHip {
+ public:
+  HomographyInitHip(svoh_ctx* ctx, const InitializationOptions& init_options, const FeatureTrackerOptions& tracker_options,
+                    const std::shared_ptr<DetectorHip>& detector);
+  InitResult addFrameBundle(const FrameBundle::Ptr& frames_cur) override;
+};
+
+// svo::TwoPointInit (initialization.h, initialization.cpp:217-289) on one camera: the translation between the reference
+// frame and the current one under the rotation the absolute orientation priors give (a gyroscope), then the triangulation.
+// Without a prior set since the last call: kFailure before anything else (every call clears the flag).  Fewer inliers than
+// init_min_inliers: kNoKeyframe.  A failed triangulation: kFailure.  Neither resets the initialiser; the caller goes on
+// with the next frame, whose tracks are longer.
+// Deviations: (1) the estimator -- opengv's RANSAC (100 iterations at most, probability 0.995) cannot be restated,
+// svoh_translation_ransac_batch stands in its place with the reference's score; (2) its hypothesis count and seed are
+// options (n_hypotheses, seed); (3) more than 1024 matches: std::runtime_error (the estimator's limit); (4) the threshold
+// is computed at every call (the reference keeps the first call's in a function-level static).
+class TwoPointInitHip : public AbstractInitializationHip {
+ public:
+  TwoPointInitHip(svoh_ctx* ctx, const InitializationOptions& init_options, const FeatureTrackerOptions& tracker_options,
+                  const std::shared_ptr<DetectorHip>& detector);
+  InitResult addFrameBundle(const FrameBundle::Ptr& frames_cur) override;
 };
 
 #endif  // SVOH_INIT_MATH_ONLY

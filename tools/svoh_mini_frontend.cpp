@@ -40,6 +40,13 @@
 // holds the reference frame and every frame from the success on; frontend.csv has a row per frame from the success on;
 // <out>/bootstrap.csv has one line per initialiser call: frame, result, n_tracked, disparity, n_inliers, n_triangulated,
 // scale, ms_ransac.  Unset: the tool prints and writes exactly what it does without the switch.
+// init_method: TwoPoint runs TwoPointInitHip instead, the initialiser for a camera with a gyroscope.  The rotation between
+// consecutive frames is read from <dataset_root>/mav0/imu_prior.csv (svoh_mini_stereo's format: one line per frame, qw qx qy qz of
+// R_imu(k)_imu(k-1)) or, without that file, integrated from mav0/imu0/data.csv (io::relativeRotationPrior, zero bias); with neither
+// the tool refuses to start.  The priors are chained from the command line's first pose, R_imu_world(k) = R_imu(k)_imu(k-1)
+// R_imu_world(k-1), and the initialiser gets R_cam_imu R_imu_world(k) (frame_handler_mono.cpp:70-75); a frame without a prior gets
+// none and the initialiser answers kFailure for it.  kNoKeyframe and kFailure go on with the next frame.  FivePoint, OneShot and
+// anything else stay refused by name.
 // n_streams > 1 (independent camera streams need no exchange): that many host threads, each
 // with its own svoh_ctx (own HIP stream) and its own copy of the chain's state, run the same sequence side by side on
 // ONE GPU; stream k > 0 writes into <out>/stream<k>/.  At EuRoC sizes a stream keeps the GPU busy for a small part
@@ -63,6 +70,7 @@
 // A frame's timestamp in the trajectory file is its image's.
 #include <sys/stat.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -70,6 +78,8 @@
 #include <cstring>
 #include <memory>
 #include <deque>
+#include <fstream>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -86,6 +96,45 @@ static double now_ms()
 }
 
 namespace {
+// SVOH_MINI_BOOTSTRAP with init_method: TwoPoint -- per frame R_imu(k)_imu(k-1), and whether it was really read / integrated
+struct RotationPriors {
+  std::vector<svoh::Quat> R_new_old;
+  std::vector<bool> have;
+  size_t count() const { size_t c = 0; for (bool h : have) c += h; return c; }
+};
+
+RotationPriors loadRotationPriors(const std::string& root, const io::EurocSequence& seq, size_t n_frames)
+{
+  RotationPriors p;
+  std::ifstream in(root + "/mav0/imu_prior.csv");
+  std::string line;
+  while (std::getline(in, line)) {
+    if (line.empty() || line[0] == '#') continue;
+    for (char& c : line) if (c == ',') c = ' ';
+    std::istringstream ss(line);
+    svoh::Quat q{ 1, 0, 0, 0 };
+    const bool parsed = static_cast<bool>(ss >> q.w >> q.x >> q.y >> q.z);   // a short or garbled line: no prior for that frame
+    p.R_new_old.push_back(parsed ? svoh::normalized(q) : svoh::Quat{ 1, 0, 0, 0 });
+    p.have.push_back(parsed);
+  }
+  if (!p.R_new_old.empty()) return p;
+  // the raw gyroscope of an EuRoC folder, integrated between the camera timestamps as ImuHandler::getRelativeRotationPrior does
+  // (no bias estimate here: zero); R_new_old is the inverse of what it returns
+  const std::vector<io::ImuMeasurement> imu = io::readEurocImu(root);
+  if (imu.empty()) return p;
+  const double bias[3] = { 0.0, 0.0, 0.0 };
+  p.R_new_old.assign(n_frames, svoh::Quat{ 1, 0, 0, 0 });
+  p.have.assign(n_frames, false);
+  for (size_t k = 1; k < n_frames; ++k) {
+    svoh::Quat R_old_new;
+    if (io::relativeRotationPrior(imu, (double)seq.cam_ts[k - 1] * 1e-9, (double)seq.cam_ts[k] * 1e-9, bias, 0.0, 0.01, &R_old_new)) {
+      p.R_new_old[k] = svoh::Quat{ R_old_new.w, -R_old_new.x, -R_old_new.y, -R_old_new.z };
+      p.have[k] = true;
+    }
+  }
+  return p;
+}
+
 struct StreamResult { size_t n_done = 0, n_kfs = 0; double sum_ms = 0, wall_ms = 0; std::string error; };
 
 // one line of SVOH_MINI_SPEC
@@ -147,7 +196,8 @@ std::vector<StreamSpec> load_specs(const char* path)
 // one camera stream through the whole chain; images are decoded beforehand and shared read-only
 void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& images, const std::vector<io::RigCamera>& rig,
                 io::FrontendParams params, const std::string& out_dir, const Transformation& T0, float depth_min, float depth_mean,
-                float depth_max, size_t kf_every, std::atomic<int>* start_gate, int n_streams, StreamResult* out, const StreamSpec* spec = nullptr)
+                float depth_max, size_t kf_every, std::atomic<int>* start_gate, int n_streams, StreamResult* out, const StreamSpec* spec = nullptr,
+                const RotationPriors* rotation_priors = nullptr)
 {
   try {
     size_t min_tracked = getenv("SVOH_MINI_MIN_TRACKED") ? (size_t)atol(getenv("SVOH_MINI_MIN_TRACKED")) : 60;   // (tests raise it to make the rule fire)
@@ -281,11 +331,17 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
     };
     // SVOH_MINI_BOOTSTRAP: the initialiser in front of the chain
     const bool bootstrap = getenv("SVOH_MINI_BOOTSTRAP") != nullptr && atoi(getenv("SVOH_MINI_BOOTSTRAP")) != 0;
-    std::unique_ptr<HomographyInitHip> initializer;
+    std::unique_ptr<AbstractInitializationHip> initializer;
     FILE* fb = nullptr;
     bool initialised = !bootstrap;
+    const bool two_point = bootstrap && params.init.init_type == InitializerType::kTwoPoint;
+    if (two_point && !rotation_priors) throw std::runtime_error("bootstrap: init_method TwoPoint without rotation priors");
+    // R_imu_world of the frame before, chained from the first pose (T0 is T_cam_world of frame 0, T_B_C is T_imu_cam)
+    svoh::Quat R_imu_world = svoh::normalized(svoh::mul(rig[0].T_B_C.q, T0.q));
     if (bootstrap) {
-      initializer.reset(new HomographyInitHip(ctx, params.init, params.tracker, std::make_shared<DetectorHip>(ctx, params.detector, cam.width, cam.height)));
+      const std::shared_ptr<DetectorHip> init_detector = std::make_shared<DetectorHip>(ctx, params.detector, cam.width, cam.height);
+      if (two_point) initializer.reset(new TwoPointInitHip(ctx, params.init, params.tracker, init_detector));
+      else initializer.reset(new HomographyInitHip(ctx, params.init, params.tracker, init_detector));
       fb = fopen((out_dir + "/bootstrap.csv").c_str(), "w");
       if (!fb) throw std::runtime_error("cannot write into " + out_dir);
       fprintf(fb, "frame,result,n_tracked,disparity,n_inliers,n_triangulated,scale,ms_ransac\n");
@@ -329,13 +385,22 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
         if (!initializer->have_depth_prior_) initializer->setDepthPrior(depth_mean);
         FrameBundle::Ptr b_cur(new FrameBundle);
         b_cur->frames_.push_back(frame);
+        if (two_point) {   // frame_handler_mono.cpp:70-75; frame 0 has the command line's orientation
+          const RotationPriors& pr = *rotation_priors;
+          const bool have = k == 0 || (order[k] < pr.have.size() && pr.have[order[k]]);
+          if (k > 0 && have) R_imu_world = svoh::normalized(svoh::mul(pr.R_new_old[order[k]], R_imu_world));
+          if (have) initializer->setAbsoluteOrientationPrior(svoh::normalized(svoh::mul(frame->T_cam_imu().q, R_imu_world)));
+        }
         if (svoh_set_kernel_timing(ctx, 1) != SVOH_OK) throw std::runtime_error(svoh_last_error_string(ctx));   // (ms_ransac: the estimator's kernel time)
         const InitResult res = initializer->addFrameBundle(b_cur);
         if (svoh_set_kernel_timing(ctx, 0) != SVOH_OK) throw std::runtime_error(svoh_last_error_string(ctx));
-        const HomographyInitHip::Statistics& st = initializer->stats_;
-        fprintf(fb, "%zu,%s,%zu,%.6f,%zu,%zu,%.9g,%.4f\n", k, res == InitResult::kSuccess ? "kSuccess" : res == InitResult::kFailure ? "kFailure" : "kTracking", st.n_tracked,
+        const AbstractInitializationHip::Statistics& st = initializer->stats_;
+        fprintf(fb, "%zu,%s,%zu,%.6f,%zu,%zu,%.9g,%.4f\n", k,
+                res == InitResult::kSuccess ? "kSuccess" : res == InitResult::kFailure ? "kFailure" : res == InitResult::kNoKeyframe ? "kNoKeyframe" : "kTracking", st.n_tracked,
                 st.disparity, st.n_inliers, st.n_triangulated, st.scale, st.ms_ransac);
-        if (res != InitResult::kSuccess) continue;   // kTracking; kFailure has reset the initialiser: the next frame starts over
+        // kTracking; the homography's kFailure has reset the initialiser, the next frame starts over; the two-point initialiser's
+        // kNoKeyframe and kFailure keep the tracks, the next frame tries again
+        if (res != InitResult::kSuccess) continue;
         // both frames become keyframes and carry the landmarks (:81-98, 100, 111)
         const FramePtr ref = initializer->frames_ref_->at(0);
         for (size_t i = 0; i < frame->num_features_; ++i) if (frame->landmark_vec_[i]) next_point_id = std::max(next_point_id, frame->landmark_vec_[i]->id_ + 1);
@@ -634,11 +699,18 @@ int main(int argc, char** argv)
     const bool lockstep = argc > 18 && std::string(argv[18]) == "lockstep";
     if (argc > 18 && !lockstep && std::string(argv[18]) != "threads") throw std::runtime_error("mode must be threads or lockstep");
     if (n_streams < 1 || n_streams > (lockstep ? 256 : 64)) throw std::runtime_error("n_streams out of range");
+    RotationPriors rotation_priors;   // of SVOH_MINI_BOOTSTRAP with init_method: TwoPoint
     if (getenv("SVOH_MINI_BOOTSTRAP") && atoi(getenv("SVOH_MINI_BOOTSTRAP")) != 0) {
       if (lockstep) throw std::runtime_error("SVOH_MINI_BOOTSTRAP: the lock-step mode has no initialiser");
       if (n_streams != 1 || !specs.empty()) throw std::runtime_error("SVOH_MINI_BOOTSTRAP: one stream, no SVOH_MINI_SPEC");
-      if (params.init.init_method != "Homography")
-        throw std::runtime_error("SVOH_MINI_BOOTSTRAP: init_method " + params.init.init_method + " is not built (only Homography is)");
+      if (params.init.init_method != "Homography" && params.init.init_method != "TwoPoint")
+        throw std::runtime_error("SVOH_MINI_BOOTSTRAP: init_method " + params.init.init_method + " is not built (only Homography and TwoPoint are)");
+      if (params.init.init_method == "TwoPoint") {
+        rotation_priors = loadRotationPriors(argv[1], seq, std::min(seq.size(), max_frames));
+        if (rotation_priors.count() == 0)
+          throw std::runtime_error(std::string("SVOH_MINI_BOOTSTRAP: init_method TwoPoint needs a rotation prior, and ") + argv[1] +
+                                   " has neither mav0/imu_prior.csv nor mav0/imu0/data.csv");
+      }
     }
     std::vector<io::GrayImage> images;
     for (size_t k = 0; k < seq.size() && k < max_frames; ++k) images.push_back(io::readPngGray(seq.cam0_files[k]));
@@ -698,9 +770,10 @@ int main(int argc, char** argv)
       const std::string dir = out_dir + "/stream" + std::to_string(s);
       (void)mkdir(dir.c_str(), 0755);
       threads.emplace_back(run_stream, std::cref(seq), std::cref(images), std::cref(rig), params, dir, std::cref(T0), depth_min, depth_mean,
-                           depth_max, kf_every, &gate, n_streams, &results[(size_t)s], (const StreamSpec*)nullptr);
+                           depth_max, kf_every, &gate, n_streams, &results[(size_t)s], (const StreamSpec*)nullptr, (const RotationPriors*)nullptr);
     }
-    run_stream(seq, images, rig, params, out_dir, T0, depth_min, depth_mean, depth_max, kf_every, &gate, n_streams, &results[0]);
+    run_stream(seq, images, rig, params, out_dir, T0, depth_min, depth_mean, depth_max, kf_every, &gate, n_streams, &results[0], nullptr,
+               rotation_priors.count() ? &rotation_priors : nullptr);
     for (std::thread& t : threads) t.join();
     for (const StreamResult& r : results) if (!r.error.empty()) throw std::runtime_error(r.error);
     printf("svoh_mini_frontend: %zu frames, %.3f ms/frame on the GPU path, %zu keyframes alive\n", results[0].n_done + 1,
