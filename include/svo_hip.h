@@ -1185,6 +1185,71 @@ typedef struct svoh_translation_result {
 int svoh_translation_ransac_batch(svoh_ctx* ctx, const svoh_init_options* options, int n_problems,
                                   const svoh_translation_problem* problems, svoh_translation_result* results, uint8_t* masks);
 
+/* ---- essential-matrix estimator of the mono bootstrap (csrc/essential.hip; DESIGN.md, "FivePoint initialiser") ----
+ * Stands where svo::FivePointInit runs opengv's RANSAC over CentralRelativePoseSacProblem with Nister's solver
+ * (src/svo/src/initialization.cpp:292-359): opengv's sampling and early stop cannot be restated, so this is an estimator
+ * of our own whose result is a function of its inputs alone; its score is the TwoPoint estimator's.  Per problem: n
+ * matches as unit bearing vectors (f_cur, f_ref: n x 3 doubles, host), thresh (the reference:
+ * 1 - cos(getAngleError(reproj_error_thresh))), a 64-bit seed; all n_hypotheses hypotheses are run.  The model is
+ * f_cur ~ R f_ref + t / lambda, so f_cur^T [t]x R f_ref = 0.
+ *   1. Hypothesis h draws mix(seed ^ mix((h << 8) + d)) mod n (mix: as above) for d = 0, 1, ... < 64 until it has five
+ *      different indices; a hypothesis that does not reach five is degenerate.
+ *   2. All real E with f_cur^T E f_ref = 0 for the five, det E = 0 and 2 E E^T E - tr(E E^T) E = 0, by Nister's route:
+ *      an orthonormal basis (X, Y, Z, W) of the null space of the five rows f_cur (x) f_ref (Gauss-Jordan with full
+ *      pivoting, then modified Gram-Schmidt), E = x X + y Y + z Z + W, the ten cubic constraints over the monomials
+ *      x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1 reduced on the first ten columns by
+ *      Gauss-Jordan with row pivoting, z times the rows of x^2, y^2, xy taken from the rows of x^2z, y^2z, xyz, and the
+ *      determinant of the three rows left (x p3(z) + y p3(z) + p4(z)): a polynomial of degree 10 in z.  Its real roots:
+ *      those of its d-th derivative, d = 9 ... 0, each sought between neighbouring roots of the derivative before and the
+ *      bound 1 + max|p_i / p_10| at both ends, a sign change bisected 64 times on the doubles' ordered bit patterns
+ *      (down to two neighbouring doubles, of which the one with the smaller |value| is the root).  (x, y, 1) is the
+ *      largest cross product of two of the three rows at z.  A pivot below 1e-12 in the null space or below 1e-9 in the
+ *      elimination (a camera that only turned leaves the ten cubics dependent and those pivots at rounding's size), or
+ *      a polynomial (or bound) that is not finite, makes the hypothesis degenerate.  Candidates are ordered by ascending
+ *      root; one that is not finite is dropped.
+ *   3. E is scaled to |E|_F^2 = 2; t is the largest cross product of two of its columns, normalised; with the cofactor
+ *      matrix Cof(E): R_a = Cof(E) - [t]x E, R_b = Cof(E) + [t]x E, each made orthonormal by five steps of
+ *      R <- R (3 I - R^T R) / 2 (a root of an ill-conditioned polynomial gives an E that is essential only roughly); a
+ *      candidate whose R_a or R_b is then further than 1e-9 from orthogonal is dropped.  Of (R_a, t), (R_a, -t), (R_b, t),
+ *      (R_b, -t) the first for which all five sample matches pass rule 4 is the candidate's motion; a candidate without
+ *      one is dropped.
+ *   4. The score is the translation estimator's rule 4 with g = R f_ref and the 2 x 2 inverse computed per match; a
+ *      match whose rays are parallel under the model (f_cur.f_cur g.g - (f_cur.g)^2 < 1e-12, or a NaN) is no inlier.
+ *      The largest count wins; among equal counts the lowest h, then the lowest candidate (its position among the roots).
+ *   5. No candidate, or a winning count below 5 (always so for n < 5): status SVOH_ESSENTIAL_NO_MODEL and every other
+ *      output zero.
+ *   6. At most 10 Gauss-Newton iterations over (w, d1, d2) on the winner's inliers (the set is fixed): residual
+ *      r_i = f_cur_i . (t x R f_ref_i); R <- Exp(w) R, t <- normalise(t + b1 d1 + b2 d2), b1 = t x a / |t x a| with a the
+ *      unit axis of t's smallest |component| (the first among equals), b2 = t x b1; sums in fp64, LDL^T; it stops at
+ *      max|step| < 1e-10, a step that is not finite is not taken.
+ *   7. The mask and n_inliers are rule 4 once more with the final (R, t).
+ * n > 1024: SVOH_ERR_INVALID_ARGUMENT, nothing written.  masks: one byte per match, the problems' one after the other.
+ * Blocking; one workgroup per problem, and a problem's result does not depend on what else is in the batch. */
+enum { SVOH_ESSENTIAL_OK = 0, SVOH_ESSENTIAL_NO_MODEL = 1 };
+typedef struct svoh_essential_problem {
+  int32_t n;
+  int32_t reserved;
+  const double* f_cur;            /* n x 3 */
+  const double* f_ref;            /* n x 3 */
+  double thresh;
+  uint64_t seed;
+} svoh_essential_problem;
+typedef struct svoh_essential_result {
+  double R[9];                    /* row-major, R_cur_ref */
+  double t[3];                    /* unit: the direction of t_cur_ref */
+  int32_t best_hypothesis;
+  int32_t best_candidate;         /* the winner's position among its hypothesis' real roots, ascending */
+  int32_t n_inliers_hypothesis;   /* the winner's count, before the refinement */
+  int32_t n_inliers;              /* after it: the number of ones in the mask */
+  int32_t n_degenerate;           /* hypotheses without a sample or without a polynomial (rules 1 and 2) */
+  int32_t n_models;               /* candidates scored */
+  int32_t refine_iters;           /* Gauss-Newton iterations started */
+  int32_t status;                 /* SVOH_ESSENTIAL_* */
+  int32_t reserved[2];
+} svoh_essential_result;
+int svoh_essential_ransac_batch(svoh_ctx* ctx, const svoh_init_options* options, int n_problems,
+                                const svoh_essential_problem* problems, svoh_essential_result* results, uint8_t* masks);
+
 #ifdef __cplusplus
 }
 #endif

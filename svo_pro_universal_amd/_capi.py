@@ -235,9 +235,23 @@ class svoh_translation_result(C.Structure):
                 ("n_inliers", C.c_int32), ("n_degenerate", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+SVOH_ESSENTIAL_OK, SVOH_ESSENTIAL_NO_MODEL = 0, 1
+
+
+class svoh_essential_problem(C.Structure):
+    _fields_ = [("n", C.c_int32), ("reserved", C.c_int32), ("f_cur", C.c_void_p), ("f_ref", C.c_void_p),
+                ("thresh", C.c_double), ("seed", C.c_uint64)]
+
+
+class svoh_essential_result(C.Structure):
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("best_hypothesis", C.c_int32), ("best_candidate", C.c_int32),
+                ("n_inliers_hypothesis", C.c_int32), ("n_inliers", C.c_int32), ("n_degenerate", C.c_int32), ("n_models", C.c_int32),
+                ("refine_iters", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 def default_init_options(**kw):
-    """The initialisers' estimators (include/svo_hip.h, svoh_homography_ransac_batch, svoh_translation_ransac_batch):
-    2000 hypotheses."""
+    """The initialisers' estimators (include/svo_hip.h, svoh_homography_ransac_batch, svoh_translation_ransac_batch,
+    svoh_essential_ransac_batch): 2000 hypotheses."""
     o = svoh_init_options(n_hypotheses=2000)
     for k, v in kw.items():
         if not hasattr(o, k):
@@ -355,6 +369,8 @@ EXPORTS = [
     "svoh_homography_ransac_batch",
     # ... and the translation estimator under a known rotation (the TwoPoint initialiser)
     "svoh_translation_ransac_batch",
+    # ... and the essential-matrix estimator (csrc/essential.hip; the FivePoint initialiser)
+    "svoh_essential_ransac_batch",
 ]
 
 
@@ -507,6 +523,8 @@ def load(path=None):
                                                  P(svoh_homography_result), C.c_void_p]
     lib.svoh_translation_ransac_batch.argtypes = [C.c_void_p, P(svoh_init_options), C.c_int, P(svoh_translation_problem),
                                                   P(svoh_translation_result), C.c_void_p]
+    lib.svoh_essential_ransac_batch.argtypes = [C.c_void_p, P(svoh_init_options), C.c_int, P(svoh_essential_problem),
+                                                P(svoh_essential_result), C.c_void_p]
     lib.svoh_histogram_angle_bins.argtypes = [C.c_void_p, C.c_int, P(svoh_frame_t), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.svoh_detect_fill_features.argtypes = [P(svoh_detector_options), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int32)]

@@ -581,6 +581,31 @@ def _homography_ransac(self, problems, options=None):
     return [res[i] for i in range(n_pb)], [masks[off[i]:off[i + 1]].copy() for i in range(n_pb)]
 
 
+def _essential_ransac(self, problems, options=None):
+    """svoh_essential_ransac_batch: the essential-matrix estimator of the mono bootstrap (the FivePoint initialiser) for a
+    batch of problems.
+    problems: list of (f_cur [n,3], f_ref [n,3], thresh, seed) -- unit bearing vectors, thresh = 1 - cos(angle error).
+    Returns (results: list of svoh_essential_result, masks: list of uint8 arrays [n])."""
+    opt = options if options is not None else capi.default_init_options()
+    n_pb = len(problems)
+    pbs = (capi.svoh_essential_problem * max(1, n_pb))()
+    res = (capi.svoh_essential_result * max(1, n_pb))()
+    keep, sizes = [], []
+    for i, (f_cur, f_ref, thresh, seed) in enumerate(problems):
+        a = np.ascontiguousarray(f_cur, dtype=np.float64).reshape(-1, 3)
+        b = np.ascontiguousarray(f_ref, dtype=np.float64).reshape(-1, 3)
+        if a.shape != b.shape:
+            raise ValueError("f_cur and f_ref must have the same shape")
+        keep += [a, b]
+        sizes.append(a.shape[0])
+        pbs[i].n, pbs[i].f_cur, pbs[i].f_ref = a.shape[0], a.ctypes.data, b.ctypes.data
+        pbs[i].thresh, pbs[i].seed = float(thresh), int(seed) & 0xFFFFFFFFFFFFFFFF
+    masks = np.zeros(max(1, sum(sizes)), np.uint8)
+    self._check(self.lib.svoh_essential_ransac_batch(self.h, C.byref(opt), n_pb, pbs, res, masks.ctypes.data))
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+    return [res[i] for i in range(n_pb)], [masks[off[i]:off[i + 1]].copy() for i in range(n_pb)]
+
+
 def _translation_ransac(self, problems, options=None):
     """svoh_translation_ransac_batch: the translation estimator of the mono bootstrap with a rotation prior (the TwoPoint
     initialiser) for a batch of problems.
@@ -705,6 +730,7 @@ Context.optimize_pose = _optimize_pose
 Context.optimize_points = _optimize_points
 Context.homography_ransac = _homography_ransac
 Context.translation_ransac = _translation_ransac
+Context.essential_ransac = _essential_ransac
 Context.klt_track_batch = _klt_track_batch
 Context.klt_track_indexed = _klt_track_indexed
 Context.update_seeds_device = _update_seeds_device

@@ -419,6 +419,32 @@ size_t estimateTranslation(svoh_ctx* ctx, const std::vector<double>& f_cur, cons
   return res.status == SVOH_TRANSLATION_OK ? (size_t)res.n_inliers : 0;
 }
 
+size_t estimateRelativePose(svoh_ctx* ctx, const std::vector<double>& f_cur, const std::vector<double>& f_ref, double thresh, uint64_t seed,
+                            int n_hypotheses, double R_cur_ref[9], double t_cur_ref[3], std::vector<uint8_t>* inliers, svoh_essential_result* result,
+                            double* ms_kernel)
+{
+  if (f_cur.size() != f_ref.size() || f_cur.size() % 3 != 0) throw std::runtime_error("estimateRelativePose: f_cur and f_ref differ in size");
+  const size_t N = f_cur.size() / 3;
+  if (N > 1024) throw std::runtime_error("estimateRelativePose: more than 1024 matches (svoh_essential_ransac_batch's limit)");
+  svoh_init_options opt{};
+  opt.n_hypotheses = n_hypotheses;
+  svoh_essential_problem pb{};
+  pb.n = (int32_t)N; pb.f_cur = f_cur.data(); pb.f_ref = f_ref.data(); pb.thresh = thresh; pb.seed = seed;
+  svoh_essential_result res{};
+  std::vector<uint8_t> mask(N ? N : 1, 0);
+  if (svoh_essential_ransac_batch(ctx, &opt, 1, &pb, &res, mask.data()) != SVOH_OK)
+    throw std::runtime_error(std::string("svoh_essential_ransac_batch: ") + svoh_last_error_string(ctx));
+  if (result) *result = res;
+  if (ms_kernel) {
+    float ms = -1.0f;
+    *ms_kernel = svoh_last_kernel_ms(ctx, &ms) == SVOH_OK ? (double)ms : -1.0;
+  }
+  for (int i = 0; i < 9; ++i) R_cur_ref[i] = res.R[i];   // zero without a model
+  for (int i = 0; i < 3; ++i) t_cur_ref[i] = res.t[i];
+  if (inliers) { mask.resize(N); inliers->swap(mask); }
+  return res.status == SVOH_ESSENTIAL_OK ? (size_t)res.n_inliers : 0;
+}
+
 namespace initialization_utils {
 
 void triangulatePoints(const Frame& frame_cur, const Frame& frame_ref, const Transformation& T_cur_ref, double reprojection_threshold,
@@ -689,6 +715,51 @@ InitResult TwoPointInitHip::addFrameBundle(const FrameBundle::Ptr& frames_cur)
   stats_.n_inliers = n_inliers;
   if (n_inliers < options_.init_min_inliers) return InitResult::kNoKeyframe;
   T_cur_from_ref_ = Transformation{ q_cur_ref, svoh::Vec3{ t[0], t[1], t[2] } };
+
+  double scale = 0.0;
+  const bool ok = initialization_utils::triangulateAndInitializePoints(frames_cur->at(0), frames_ref->at(0), T_cur_from_ref_, options_.reproj_error_thresh,
+                                                                       depth_at_current_frame_, options_.init_min_inliers, matches_cur_ref, &scale);
+  stats_.n_triangulated = matches_cur_ref.size();
+  if (!ok) return InitResult::kFailure;
+  stats_.scale = scale;
+  return InitResult::kSuccess;
+}
+
+// ---- FivePointInit ----------------------------------------------------------------------------------------------------
+FivePointInitHip::FivePointInitHip(svoh_ctx* ctx, const InitializationOptions& init_options, const FeatureTrackerOptions& tracker_options,
+                                   const std::shared_ptr<DetectorHip>& detector)
+    : AbstractInitializationHip(ctx, init_options, tracker_options, detector, "FivePointInitHip")
+{
+}
+
+InitResult FivePointInitHip::addFrameBundle(const FrameBundle::Ptr& frames_cur)
+{
+  stats_ = Statistics();
+  if (!frames_cur || frames_cur->size() != 1) throw std::runtime_error("FivePointInitHip: one camera per bundle");
+  if (!trackFeaturesAndCheckDisparity(frames_cur)) return InitResult::kTracking;
+
+  const FrameBundle::Ptr frames_ref = tracker_.getOldestFrameInTrack(0);
+  const Frame& frame_ref = *frames_ref->at(0);
+  const Frame& frame_cur = *frames_cur->at(0);
+  initialization_utils::FeatureMatches matches_cur_ref;
+  feature_tracking_utils::getFeatureMatches(frame_cur.track_id_vec_.data(), frame_cur.num_features_, frame_ref.track_id_vec_.data(), frame_ref.num_features_, &matches_cur_ref);
+  const size_t n = matches_cur_ref.size();
+  std::vector<double> f_cur(3 * n), f_ref(3 * n);   // initialization_utils::copyBearingVectors
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < 3; ++k) {
+      f_cur[3 * i + k] = frame_cur.f_vec_[3 * matches_cur_ref[i].first + k];
+      f_ref[3 * i + k] = frame_ref.f_vec_[3 * matches_cur_ref[i].second + k];
+    }
+
+  // the model: 1 - cos(Frame::getAngleError(reproj_error_thresh)) (pinhole_projection.hpp:72-76)
+  const double angle_error = std::atan(options_.reproj_error_thresh / (2.0 * frame_cur.cam.fx)) + std::atan(options_.reproj_error_thresh / (2.0 * frame_cur.cam.fy));
+  const double inlier_threshold = 1.0 - std::cos(angle_error);
+  double R_cur_ref[9], t[3], ms = -1.0;
+  const size_t n_inliers = estimateRelativePose(ctx_, f_cur, f_ref, inlier_threshold, options_.seed, options_.n_hypotheses, R_cur_ref, t, nullptr, nullptr, &ms);
+  stats_.ms_ransac = ms;
+  stats_.n_inliers = n_inliers;
+  if (n_inliers < options_.init_min_inliers) return InitResult::kNoKeyframe;   // (no model: zero inliers)
+  T_cur_from_ref_ = Transformation{ svoh::normalized(vk::quaternionFromRotation(R_cur_ref)), svoh::Vec3{ t[0], t[1], t[2] } };
 
   double scale = 0.0;
   const bool ok = initialization_utils::triangulateAndInitializePoints(frames_cur->at(0), frames_ref->at(0), T_cur_from_ref_, options_.reproj_error_thresh,

@@ -2,6 +2,7 @@
 // ("Homography initialiser").  Counterparts in the reference:
 //   svo::HomographyInit::addFrameBundle            src/svo/src/initialization.cpp:86-161
 //   svo::TwoPointInit::addFrameBundle              src/svo/src/initialization.cpp:164-289
+//   svo::FivePointInit::addFrameBundle             src/svo/src/initialization.cpp:292-359
 //   vk::estimateHomography                          src/vikit/vikit_common/src/homography.cpp:19-136
 //   HomographyDecomp::removeScale, HomographyDecompInria::decompose
 //                                                   src/vikit/vikit_common/include/vikit/homography_decomp.h:121-126, 283-430
@@ -14,7 +15,7 @@
 //
 // The maths of this file makes no device call and needs nothing but this header and svoh_math.h: a CPU program compiles
 // svo_hip_init.cpp with -DSVOH_INIT_MATH_ONLY and links nothing else (tests/cpp_init).  What runs on the device
-// (estimateHomography, estimateTranslation, HomographyInitHip, TwoPointInitHip) is left out of such a build.
+// (estimateHomography, estimateTranslation, estimateRelativePose, HomographyInitHip, TwoPointInitHip, FivePointInitHip) is left out of such a build.
 #pragma once
 
 #include <cstddef>
@@ -105,6 +106,15 @@ size_t estimateTranslation(svoh_ctx* ctx, const std::vector<double>& f_cur, cons
                            double thresh, uint64_t seed, int n_hypotheses, double t_cur_ref[3], std::vector<uint8_t>* inliers = nullptr,
                            svoh_translation_result* result = nullptr, double* ms_kernel = nullptr);
 
+// The model of FivePointInit (initialization.cpp:313-337) with svoh_essential_ransac_batch where the reference runs
+// opengv's RANSAC over Nister's solver: R_cur_ref (row-major) and the unit translation t_cur_ref from unit bearing vectors
+// (3 doubles a match), thresh = 1 - cos(angle error), n_hypotheses hypotheses from `seed`.  Returns the number of inliers
+// (0: no model; R and t are then zero); inliers (may be NULL): one flag per match.  More than 1024 matches:
+// std::runtime_error.  ms_kernel (may be NULL): the kernel's device time when kernel timing is on, else -1.
+size_t estimateRelativePose(svoh_ctx* ctx, const std::vector<double>& f_cur, const std::vector<double>& f_ref, double thresh, uint64_t seed,
+                            int n_hypotheses, double R_cur_ref[9], double t_cur_ref[3], std::vector<uint8_t>* inliers = nullptr,
+                            svoh_essential_result* result = nullptr, double* ms_kernel = nullptr);
+
 namespace initialization_utils {
 // the Frame forms (initialization.cpp:729-840): landmarks are made and hung on both frames, the current frame gets its pose
 void triangulatePoints(const Frame& frame_cur, const Frame& frame_ref, const Transformation& T_cur_ref, double reprojection_threshold,
@@ -193,6 +203,21 @@ class TwoPointInitHip : public AbstractInitializationHip {
  public:
   TwoPointInitHip(svoh_ctx* ctx, const InitializationOptions& init_options, const FeatureTrackerOptions& tracker_options,
                   const std::shared_ptr<DetectorHip>& detector);
+  InitResult addFrameBundle(const FrameBundle::Ptr& frames_cur) override;
+};
+
+// svo::FivePointInit (initialization.h, initialization.cpp:292-359) on one camera: the relative pose between the reference
+// frame and the current one from the matches alone, then the triangulation.  Too few tracks or too little disparity:
+// kTracking.  Fewer inliers than init_min_inliers, or no model: kNoKeyframe.  A failed triangulation: kFailure.  Neither
+// resets the initialiser; the caller goes on with the next frame, whose tracks are longer.
+// Deviations: (1) the estimator -- opengv's RANSAC (100 iterations at most, probability 0.995) cannot be restated,
+// svoh_essential_ransac_batch stands in its place with the score of the TwoPoint estimator; (2) its hypothesis count and
+// seed are options (n_hypotheses, seed); (3) more than 1024 matches: std::runtime_error (the estimator's limit); (4) the
+// threshold is computed at every call (the reference keeps the first call's in a function-level static).
+class FivePointInitHip : public AbstractInitializationHip {
+ public:
+  FivePointInitHip(svoh_ctx* ctx, const InitializationOptions& init_options, const FeatureTrackerOptions& tracker_options,
+                   const std::shared_ptr<DetectorHip>& detector);
   InitResult addFrameBundle(const FrameBundle::Ptr& frames_cur) override;
 };
 

@@ -45,8 +45,10 @@
 // R_imu(k)_imu(k-1)) or, without that file, integrated from mav0/imu0/data.csv (io::relativeRotationPrior, zero bias); with neither
 // the tool refuses to start.  The priors are chained from the command line's first pose, R_imu_world(k) = R_imu(k)_imu(k-1)
 // R_imu_world(k-1), and the initialiser gets R_cam_imu R_imu_world(k) (frame_handler_mono.cpp:70-75); a frame without a prior gets
-// none and the initialiser answers kFailure for it.  kNoKeyframe and kFailure go on with the next frame.  FivePoint, OneShot and
-// anything else stay refused by name.
+// none and the initialiser answers kFailure for it.  kNoKeyframe and kFailure go on with the next frame.
+// SVOH_MINI_BOOTSTRAP=2 runs init_method: FivePoint as well (FivePointInitHip: the relative pose from the matches alone; the
+// default of the parameter loader, so a file that names no method runs it); under the value 1 FivePoint stays refused by name,
+// with the value that runs it in the message.  OneShot and anything else stay refused by name under either value.
 // n_streams > 1 (independent camera streams need no exchange): that many host threads, each
 // with its own svoh_ctx (own HIP stream) and its own copy of the chain's state, run the same sequence side by side on
 // ONE GPU; stream k > 0 writes into <out>/stream<k>/.  At EuRoC sizes a stream keeps the GPU busy for a small part
@@ -341,6 +343,7 @@ void run_stream(const io::EurocSequence& seq, const std::vector<io::GrayImage>& 
     if (bootstrap) {
       const std::shared_ptr<DetectorHip> init_detector = std::make_shared<DetectorHip>(ctx, params.detector, cam.width, cam.height);
       if (two_point) initializer.reset(new TwoPointInitHip(ctx, params.init, params.tracker, init_detector));
+      else if (params.init.init_type == InitializerType::kFivePoint) initializer.reset(new FivePointInitHip(ctx, params.init, params.tracker, init_detector));
       else initializer.reset(new HomographyInitHip(ctx, params.init, params.tracker, init_detector));
       fb = fopen((out_dir + "/bootstrap.csv").c_str(), "w");
       if (!fb) throw std::runtime_error("cannot write into " + out_dir);
@@ -703,8 +706,11 @@ int main(int argc, char** argv)
     if (getenv("SVOH_MINI_BOOTSTRAP") && atoi(getenv("SVOH_MINI_BOOTSTRAP")) != 0) {
       if (lockstep) throw std::runtime_error("SVOH_MINI_BOOTSTRAP: the lock-step mode has no initialiser");
       if (n_streams != 1 || !specs.empty()) throw std::runtime_error("SVOH_MINI_BOOTSTRAP: one stream, no SVOH_MINI_SPEC");
-      if (params.init.init_method != "Homography" && params.init.init_method != "TwoPoint")
-        throw std::runtime_error("SVOH_MINI_BOOTSTRAP: init_method " + params.init.init_method + " is not built (only Homography and TwoPoint are)");
+      const int bootstrap_level = atoi(getenv("SVOH_MINI_BOOTSTRAP"));   // 2: FivePoint as well; every other non-zero value means 1
+      if (params.init.init_method == "FivePoint" && bootstrap_level != 2)
+        throw std::runtime_error("SVOH_MINI_BOOTSTRAP=1: init_method FivePoint is not run (only Homography and TwoPoint are); SVOH_MINI_BOOTSTRAP=2 runs it");
+      if (params.init.init_method != "Homography" && params.init.init_method != "TwoPoint" && params.init.init_method != "FivePoint")
+        throw std::runtime_error("SVOH_MINI_BOOTSTRAP: init_method " + params.init.init_method + " is not built (only Homography, TwoPoint and FivePoint are)");
       if (params.init.init_method == "TwoPoint") {
         rotation_priors = loadRotationPriors(argv[1], seq, std::min(seq.size(), max_frames));
         if (rotation_priors.count() == 0)
