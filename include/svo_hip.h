@@ -1196,7 +1196,8 @@ int svoh_translation_ransac_batch(svoh_ctx* ctx, const svoh_init_options* option
  *      different indices; a hypothesis that does not reach five is degenerate.
  *   2. All real E with f_cur^T E f_ref = 0 for the five, det E = 0 and 2 E E^T E - tr(E E^T) E = 0, by Nister's route:
  *      an orthonormal basis (X, Y, Z, W) of the null space of the five rows f_cur (x) f_ref (Gauss-Jordan with full
- *      pivoting, then modified Gram-Schmidt), E = x X + y Y + z Z + W, the ten cubic constraints over the monomials
+ *      pivoting, then modified Gram-Schmidt, then a turn by a fixed orthogonal 4 x 4 that takes the basis out of the
+ *      special positions exact data puts it in), E = x X + y Y + z Z + W, the ten cubic constraints over the monomials
  *      x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1 reduced on the first ten columns by
  *      Gauss-Jordan with row pivoting, z times the rows of x^2, y^2, xy taken from the rows of x^2z, y^2z, xyz, and the
  *      determinant of the three rows left (x p3(z) + y p3(z) + p4(z)): a polynomial of degree 10 in z.  Its real roots:

@@ -89,8 +89,26 @@ SVOH_HD bool essential_sample(unsigned long long seed, unsigned h, unsigned n, u
   return kept == 5;
 }
 
+// A fixed orthogonal 4 x 4 (the left product of the quaternion (1, 2, 4, 10) / 11 times the right product of (2, 3, 6, 0) / 7;
+// no entry is zero): essential_turn_basis takes a basis in special position to one in general position (essential_solve).
+SVOH_HD double essential_turn(int i, int j)
+{
+  const int num[16] = { -28, -67, 16, -20, -53, 20, -44, -28, 44, -4, -16, -61, 20, -32, -59, 32 };
+  return (double)num[4 * i + j] / 77.0;
+}
+SVOH_HD void essential_turn_basis(double B[4][9])
+{
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+  for (int e = 0; e < 9; ++e) {
+    const double b[4] = { B[0][e], B[1][e], B[2][e], B[3][e] };
+    for (int i = 0; i < 4; ++i) B[i][e] = essential_turn(i, 0) * b[0] + essential_turn(i, 1) * b[1] + essential_turn(i, 2) * b[2] + essential_turn(i, 3) * b[3];
+  }
+}
+
 // rule 2, first step: an orthonormal basis B[4][9] of the null space of the five rows q = f_cur (x) f_ref (row-major E);
-// Gauss-Jordan with full pivoting, then modified Gram-Schmidt.  false: no usable pivot.
+// Gauss-Jordan with full pivoting, then modified Gram-Schmidt, then the fixed turn.  false: no usable pivot.
 SVOH_HD_CALL bool essential_nullspace(const double fs[5][6], double B[4][9])
 {
   double A[5][9];
@@ -138,6 +156,7 @@ SVOH_HD_CALL bool essential_nullspace(const double fs[5][6], double B[4][9])
     const double in = 1.0 / sqrt(nn);
     for (int c = 0; c < 9; ++c) B[j][c] *= in;
   }
+  essential_turn_basis(B);
   return true;
 }
 
@@ -454,7 +473,13 @@ SVOH_HD int essential_count_inliers(const double R[9], const double t[3], const 
 }
 
 // rule 2 as one call: the five staged matches in, the null-space basis, the three rows in z and the real roots out; the number
-// of roots, or -1 for a degenerate hypothesis
+// of roots, or -1 for a degenerate hypothesis.  The elimination singles out the basis: its left block has no usable pivot, the
+// polynomial no leading coefficient, or the wanted root is one of a cluster, when a solution lies at or near infinity of
+// (x, y, z) or a basis vector is itself an essential matrix.  The basis of essential_nullspace has a one and three zeros in
+// every vector and so inherits the zeros of E = [t]x: on exact matches of a camera that did not turn it is in such a special
+// position for every fifth sample.  That is a property of the basis, not of the five matches, so essential_nullspace turns
+// its basis by the fixed orthogonal matrix: general position for any data that is not built from that matrix.  A camera that
+// only turned has no usable pivot in any basis.
 SVOH_HD_CALL int essential_solve(const double fs[5][6], double B[4][9], double C[3][13], double roots[kEssentialMaxRoots])
 {
   double p[11];

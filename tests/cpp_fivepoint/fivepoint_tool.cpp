@@ -50,7 +50,7 @@ int main(int argc, char** argv)
       cols[(size_t)(3 + k) * (size_t)cap + (size_t)i] = f_ref[3 * (size_t)i + (size_t)k];
     }
 
-  long best_h = -1, n_degenerate = 0, n_models = 0;
+  long best_h = -1, n_degenerate = 0, n_models = 0, n_hold_all = 0;   // n_hold_all: hypotheses whose best candidate holds every match
   int best_count = -1, best_c = 0;
   double R0[9] = { 0 }, t0[3] = { 0 };
   if (n >= 5) {
@@ -59,6 +59,7 @@ int main(int argc, char** argv)
       double R[9], t[3];
       if (!essential_hypothesis(seed, (unsigned)h, cols.data(), cap, n, thresh, models, count, candidate, R, t)) { ++n_degenerate; continue; }
       n_models += models;
+      if (models > 0 && count == n) ++n_hold_all;
       if (models > 0 && count > best_count) {
         best_count = count; best_h = h; best_c = candidate;
         for (int k = 0; k < 9; ++k) R0[k] = R[k];
@@ -103,6 +104,7 @@ int main(int argc, char** argv)
            best_h, best_c, best_count, n_inliers, n_degenerate, n_models, iters);
     print9("R", R, 9); print9("t", t, 3); print9("R_winner", R0, 9); print9("t_winner", t0, 3);
   }
+  printf("n_hold_all %ld\n", n_hold_all);
   printf("mask");
   for (int i = 0; i < n; ++i) printf(" %d", mask[(size_t)i]);
   printf("\n");
