@@ -150,13 +150,13 @@ struct AlignKernelArgs {
   // traffic in round 2 (3.85 of 5.27 GB per 1024 x 2000 launch were these rows read again every iteration)
   double* wpk;
   int64_t slots;                        // stride of the SoA arrays
-  uint8_t* wsel;                        // selected by extractFeaturesSubset (a-3)
-  uint8_t* wvis;                        // visibility of the last evaluation
+  uint8_t* wsel;                        // selected by extractFeaturesSubset (a-3)     } byte masks that only svoh_sparse_align_evaluate reads:
+  uint8_t* wvis;                        // visibility of the last evaluation           } written in eval mode only
   svoh_align_options opt;
   int32_t lds_img_bytes;                // dynamic LDS available for image staging
   int32_t rig_build;                    // host side only: a small launch with problems of several cameras -> the instantiation that runs a rig's cameras side by side
   int32_t latency_build;                // host side only: fewer problems than compute units -> the one-wave-per-SIMD build of the 256-thread kernel
-  int32_t lds_two_per_cu;               // host side only: the launch counts on two workgroups per compute unit (launch_one sizes the image area for it)
+  int32_t lds_wg_per_cu;                // host side only: > 0: the launch counts on that many workgroups per compute unit (launch_one sizes the image area for it)
   int32_t ws_lds_bytes;                 // > 0: the feature workspace of a (small) problem lives in LDS behind the image area (512-thread geometry)
   int32_t eval_level;                   // <0: full run; >=0: evaluate once at that level
   double* eval_out;                     // [64 H][8 g][chi2][n_meas] for eval mode
@@ -414,6 +414,12 @@ __device__ __forceinline__ void patch_moments_part(
   // overlaps the interpolation of the row before instead of preceding every row's arithmetic.
   PackedRow<WB + 1> pref_r;
   PackedRow<P + 1> pref_c;
+  // a half-resident level (the reference image in LDS, the current one in global memory): the global side keeps its requests a row ahead
+  PackedRow<P + 1> c0_mixed;
+  if constexpr (RLDS && !CLDS) {
+    cur.template fetch<P + 1>(coff, c0_mixed);
+    cur.template fetch<P + 1>(coff + cur.pitch, pref_c);
+  }
   if constexpr (!RLDS) {
     PackedRow<WB + 1> r0, r1, r2;
     ref.template fetch<WB + 1>(roff, r0);
@@ -443,7 +449,8 @@ __device__ __forceinline__ void patch_moments_part(
 #pragma unroll
   for (int i = 0; i < WB; ++i)
     it2[i] = rwtl * (double)rawB[i] + rwtr * (double)rawB[i + 1] + rwbl * (double)rawA[i] + rwbr * (double)rawA[i + 1];
-  if constexpr (RLDS || CLDS) cur.template row<P + 1>(coff, curB);
+  if constexpr (RLDS && !CLDS) ImgView<false>::unpack<P + 1>(c0_mixed, curB);
+  else if constexpr (CLDS) cur.template row<P + 1>(coff, curB);
   // here: rawA = raw row 2, it1 = interp row 0, it2 = interp row 1, curB = cur row 0
 
   // the gradient-only pass has registers to spare (7 or 9 accumulators instead of 28 or 45): unrolled rows let the
@@ -467,6 +474,11 @@ __device__ __forceinline__ void patch_moments_part(
         cur.template fetch<P + 1>(crow + cur.pitch, pref_c);
       }
       asm volatile("" ::: "memory");   // keep the requests ahead of this row's arithmetic
+    } else if constexpr (RLDS && !CLDS) {   // half-resident level: reference rows from LDS, current rows from global memory a row ahead
+      ImgView<false>::unpack<P + 1>(pref_c, curB);
+      if (y + 1 < PH) cur.template fetch<P + 1>(crow + cur.pitch, pref_c);
+      asm volatile("" ::: "memory");
+      ref.template row<WB + 1>(rrow, rawB);
     } else {
       ref.template row<WB + 1>(rrow, rawB);
       cur.template row<P + 1>(crow, curB);
@@ -953,9 +965,10 @@ __device__ __forceinline__ void accumulate_camera_rows(
 // behind the pixel loop for the Jacobian rows (three doubles that need not stay in registers through it).
 // stage: this wave's 2 x 3 x 64 x 16 B staging area.  Control flow is wave-uniform (every lane runs every pass).
 constexpr int kStageDoubles = 2 * kWsPairs * 128;
-template <int P, int D, int NT, bool LDS, bool GONLY = false, bool ROB = false>
+// LDS / CLDS: where the reference and the current image of the level are (they differ on a half-resident level)
+template <int P, int D, int NT, bool LDS, bool GONLY = false, bool ROB = false, bool CLDS = LDS>
 __device__ __forceinline__ void accumulate_camera_staged(
-    const AlignKernelArgs& a, const CamPass& cd, const ImgView<LDS>& ref, const ImgView<LDS>& cur, int cw, int ch,
+    const AlignKernelArgs& a, const CamPass& cd, const ImgView<LDS>& ref, const ImgView<CLDS>& cur, int cw, int ch,
     const Rigid& Tcr, double scale, double one_plus_alpha, double beta_d, bool est_alpha, bool est_beta,
     bool robust, bool dist_jac, float weight_scale, int tid, double* stage, const double* jc,
     double (&acc)[GONLY ? D + 1 : AccLayout<D>::NACC], int& nvis, int& changed, int stride = NT)
@@ -1018,12 +1031,12 @@ __device__ __forceinline__ void accumulate_camera_staged(
         const double rv_tl = vs.x * scale - patch_center_wb;
         const int ru = (int)floor(ru_tl), rv = (int)floor(rv_tl);
         const double rsu = ru_tl - ru, rsv = rv_tl - rv;
-        patch_moments<P, D, LDS, LDS, GONLY, ROB>(ref, cur, ru, rv, rsu, rsv, cu, cv, csu, csv, one_plus_alpha, beta_d,
-                                                  robust, weight_scale, mom);
+        patch_moments<P, D, LDS, CLDS, GONLY, ROB>(ref, cur, ru, rv, rsu, rsv, cu, cv, csu, csv, one_plus_alpha, beta_d,
+                                                   robust, weight_scale, mom);
       }
     }
     if (vis) {
-      if constexpr (LDS) {   // see accumulate_camera
+      if constexpr (LDS && CLDS) {   // see accumulate_camera
 #pragma unroll
         for (int k = 0; k < AccLayout<D>::NMOM; ++k)
           if (!GONLY || k == 3 || k == 4 || k == 5 || k == 13 || k == 14) asm volatile("" : "+v"(mom[k]));
@@ -1421,13 +1434,15 @@ __device__ __attribute__((noinline)) void gn_wave_step(const AlignKernelArgs& a,
 // single-camera problem 1.5 - 4 % of its kernel (measured: register allocation and a scalar-load dependency per pass),
 // which the mono chain should not pay.
 template <int P, int NT, bool ILLUM, bool CLUSTER = false, bool ROBUST = false, int LPP = 1, bool LAT = false, bool RIG = false>
-__global__ __launch_bounds__(NT, (NT == 256 ? (LAT ? 1 : 2) : 2))   // 256 threads: two workgroups per compute unit (256 registers), the latency build one
+__global__ __launch_bounds__(NT, (NT == 256 ? (LAT ? 1 : 2) : 2))   // waves per SIMD.  256 threads: two workgroups per compute unit (256 registers), the latency build one;
+                                                                   // 128 threads: four workgroups per compute unit, two waves per SIMD and 256 registers all the same
 void sparse_align_kernel(const AlignKernelArgs a)
 {
   static_assert(!LAT || (NT == 256 && !CLUSTER && LPP == 1), "latency build: the 256-thread lane-per-patch geometry");
   static_assert(!RIG || (!CLUSTER && LPP == 1 && (LAT || NT == 512)), "rig build: the two lane-per-patch geometries of small launches");
   static_assert(LPP == 1 || (!CLUSTER && NT == 512 && LPP <= P), "rows geometry: 512 threads, no cluster mode");
-  static_assert(NT == 256 || NT == 512, "workgroups of 256 or 512 threads");
+  static_assert(NT == 128 || NT == 256 || NT == 512, "workgroups of 128, 256 or 512 threads");
+  static_assert(NT != 128 || (!CLUSTER && !LAT && !RIG && LPP == 1), "128 threads: the batch geometry only");
   constexpr bool ROWS = LPP > 1;
   constexpr int D = ILLUM ? 8 : 6;
   constexpr int NACC = AccLayout<D>::NACC;
@@ -1435,11 +1450,17 @@ void sparse_align_kernel(const AlignKernelArgs a)
 
   // LDS-DMA staging of the workspace rows (accumulate_camera_staged) in the batch geometry; the wide
   // geometries keep their LDS for finer image levels and read the workspace with ordinary loads
-  constexpr bool STAGED = NT == 256 && !ROWS;
+  constexpr bool STAGED = (NT == 256 || NT == 128) && !ROWS;
   // the levels' images through registers in the BATCH geometry only (stage_item_list): a workgroup there has a second one beside it on its compute
   // unit to fill the wait; the small-launch geometries keep the LDS-DMA requests, whose flight overlaps the problem's base phase (measured, one
   // 180-patch problem: 27.6 us outside the iterations with LDS-DMA, 31.3 with the blocking copy)
-  constexpr bool kStageRegs = NT == 256 && !LAT && !CLUSTER && !ROWS;
+  constexpr bool kStageRegs = (NT == 256 || NT == 128) && !LAT && !CLUSTER && !ROWS;
+  // Half-level residency: a level whose pair of images does not fit the image area while ONE of them does runs with that one in
+  // LDS and the other from global memory.  The 128-thread build only: its 23 KB hold levels 4 and 3 of a 640x480 pair and one
+  // image of level 2; the wider builds hold all of level 2 and not even one image of level 1.
+  constexpr bool kHalfLevel = NT == 128;
+  // The resident one is the reference image (7 rows per 4x4 patch against the current image's 5; measured against the other
+  // choice: no difference, profiles/r09_align_wg128_ab.txt).
   extern __shared__ __align__(16) unsigned char lds_img[];
   __shared__ __align__(16) double s_stage[STAGED ? NW * kStageDoubles : 2];
   __shared__ double s_jc[SVOH_MAX_CAMS][kJacConsts];   // per-camera constants of jac_rows
@@ -1607,7 +1628,11 @@ void sparse_align_kernel(const AlignKernelArgs a)
       // (65 bytes per feature, read once), and the vector-memory counter is in order -- with one feature requested ahead
       // every trip waited for the PREVIOUS trip's stores as well (round 4 stamps: 99 K cycles per 2000-feature problem,
       // 12 K per trip: 9 % of a workgroup's life in the batch)
-      constexpr int kBaseDepth = 4;
+      // (128 threads: eight, so that a 2000-feature problem is two trips there as well.  Six pairs of the headline, eight against four:
+      // 3.3243 - 3.3411 ms per step in five runs and ONE at 3.4418, against 3.3175 - 3.3762; medians 3.3365 / 3.3527, 0.5 %: inside the
+      // spread, no gain shown -- profiles/r09_align_wg128_ab.txt.  Kept for the equal number of trips, and because the committed
+      // kernels' own A/B was taken with it)
+      constexpr int kBaseDepth = NT == 128 ? 8 : 4;
       for (int i0 = tid; i0 < cd.n_features; i0 += kBaseDepth * NT) {
         FeatIn in[kBaseDepth];
 #pragma unroll
@@ -1634,8 +1659,10 @@ void sparse_align_kernel(const AlignKernelArgs a)
             sel = !(u_tl_i < 0 || v_tl_i < 0 || u_tl_i >= cols_minus_two - patch_size_wb ||
                     v_tl_i >= rows_minus_two - patch_size_wb);
           }
-          a.wsel[gi] = sel ? 1 : 0;
-          a.wvis[gi] = 0;
+          // the byte masks are what svoh_sparse_align_evaluate hands out; a run reads the row's state value alone.  (A lane's
+          // vector-memory counter returns in order: in a run these two byte stores per feature were 16 of the 40 stores a
+          // lane of a 2000-feature problem waits behind.)
+          if (eval_mode) { a.wsel[gi] = sel ? 1 : 0; a.wvis[gi] = 0; }
           if (!sel) *reinterpret_cast<double2*>(ws_pair(ws, 2, gi)) = make_double2(0.0, 0.0);
           if (sel) {
             const double dx = pwx - cd.ref_pos[0];
@@ -1712,6 +1739,21 @@ void sparse_align_kernel(const AlignKernelArgs a)
       lvl_off = 0;
       in_lds = true;
     }
+    // ... and one whose pair does not fit while one of its images does (one camera): that image alone, over the levels that
+    // are done; the passes read the other from global memory
+    bool half_lds = false;
+    if constexpr (kHalfLevel) {
+      if (!in_lds && n_cams == 1) {
+        const DevImage& him = cams[0].ref[level];
+        if (((him.w * him.h + 15) & ~15) <= a.lds_img_bytes) {
+          __syncthreads();   // the finished levels' readers are done with lds_img
+          DevImage none = him;   // (the pair's copy with an empty second image: through registers where the pairs go that way)
+          none.w = none.h = none.pitch = 0;
+          stage_image_pair<NT, kStageRegs>(lds_img, him, lds_img, none, tid);
+          half_lds = true;
+        }
+      }
+    }
     __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this thread's image requests (issued here or at the problem's start) have landed
     __syncthreads();
     if (tid == 0) {
@@ -1760,7 +1802,17 @@ void sparse_align_kernel(const AlignKernelArgs a)
               cam_t = (unsigned)(tid - cam_base);
               cam_base += cam_width;
             }
-            if (in_lds) {
+            if (kHalfLevel && half_lds) {
+              if constexpr (kHalfLevel) {   // (the batch geometry: one camera, the whole workgroup)
+                ImgView<true> ref;
+                ImgView<false> cur;
+                ref.p = (const __attribute__((address_space(3))) uint8_t*)lds_img; ref.pitch = rim.w;
+                cur.p = cim.data; cur.pitch = cim.pitch;
+                accumulate_camera_staged<P, D, NT, true, G, ROBUST, false>(a, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
+                                                                                   est_alpha, est_beta, robust, dist_jac, weight_scale, (int)cam_t,
+                                                                                   s_stage + wave * kStageDoubles, s_jc[c], acc_ref, nvis, changed, (int)cam_stride);
+              }
+            } else if (in_lds) {
               ImgView<true> ref, cur;
               ref.p = (const __attribute__((address_space(3))) uint8_t*)(lds_img + off); ref.pitch = rim.w;
               off += ((rim.w * rim.h + 15) & ~15);
@@ -1992,11 +2044,13 @@ template <int P, int NT, bool ILLUM, bool CLUSTER, bool ROBUST, int LPP = 1, boo
 static hipError_t launch_one(hipStream_t st, int grid, size_t lds, AlignKernelArgs args, int32_t* lds_img_launched)
 {
   auto kern = sparse_align_kernel<P, NT, ILLUM, CLUSTER, ROBUST, LPP, LAT, RIG>;
-  if (NT == 256 && args.lds_two_per_cu) {
+  if ((NT == 256 || NT == 128) && args.lds_wg_per_cu > 0) {
     // Two workgroups per compute unit is what the batch geometry is built on, and the budget is tight (28-29.5 KB of
     // static LDS + 51 KB of images = 79-80.5 of the 80 KB a workgroup may have).  The static part is asked of the code
     // object, not assumed: if it ever grows, the image area shrinks (a level fewer in LDS) instead of the second
     // workgroup silently not fitting -- half the throughput with every test green.
+    // (128 threads: four workgroups, 40 KB each -- 15 952 - 16 480 B static, the rest images)
+    const size_t share = kLdsPerCu / (size_t)args.lds_wg_per_cu;
     static std::atomic<size_t> static_lds_cache{ 0 };   // per instantiation; the same for every context and host thread (one code object)
     size_t static_lds = static_lds_cache.load(std::memory_order_relaxed);
     if (static_lds == 0) {
@@ -2006,7 +2060,7 @@ static hipError_t launch_one(hipStream_t st, int grid, size_t lds, AlignKernelAr
       static_lds = attr.sharedSizeBytes ? attr.sharedSizeBytes : 1;
       static_lds_cache.store(static_lds, std::memory_order_relaxed);
     }
-    const size_t room = kLdsPerCu / 2 > static_lds ? (kLdsPerCu / 2 - static_lds) & ~(size_t)15 : 0;
+    const size_t room = share > static_lds ? (share - static_lds) & ~(size_t)15 : 0;
     if (lds > room) {
       args.lds_img_bytes -= (int32_t)(lds - room);
       if (args.lds_img_bytes < 0) args.lds_img_bytes = 0;
@@ -2026,6 +2080,7 @@ template <int P, bool ILLUM, bool ROBUST>
 static hipError_t launch_nt(hipStream_t st, int nt, int lpp, int grid, size_t lds, const AlignKernelArgs& args, int32_t* lds_img_launched)
 {
   if (args.cluster > 1) return launch_one<P, 256, ILLUM, true, ROBUST>(st, grid, lds, args, lds_img_launched);
+  if (nt == 128) return launch_one<P, 128, ILLUM, false, ROBUST>(st, grid, lds, args, lds_img_launched);
   if (nt == 256) {
     if (args.latency_build) return args.rig_build ? launch_one<P, 256, ILLUM, false, ROBUST, 1, true, true>(st, grid, lds, args, lds_img_launched)
                                                   : launch_one<P, 256, ILLUM, false, ROBUST, 1, true>(st, grid, lds, args, lds_img_launched);
@@ -2046,6 +2101,12 @@ constexpr int kWsLdsMaxFeatures = 340;    // features of a problem whose workspa
 constexpr int kClusterMinFeatures = 512;
 constexpr int kClusterMaxWorkgroups = 32;
 constexpr int kClusterMaxProblems = 64;   // arrival counters: one 32-bit word per problem in a 256-byte block
+// the 128-thread batch build (decide_geometry): taken by default from this many rounds of four problems per compute unit on
+// (measured, profiles/r09_align_wg128_ab.txt, 2000-feature problems on 256 compute units: one round -- 1024 problems -- no gain; two
+// rounds between 2 % faster and 2 % slower; four rounds, 4096 problems, 1.2 - 3 % faster in every pair.  4096 is the ONLY size
+// measured as a gain: nothing was measured between 2048 and 4096, above 4096, or for problems of few features, whose second wave
+// stands empty; that larger launches gain as well rests on the argument that a launch's tail weighs less the longer it is)
+constexpr int kAlign128MinRounds = 4;
 
 static int validate_options(svoh_ctx* ctx, const svoh_align_options* o)
 {
@@ -2078,15 +2139,16 @@ struct SplitArgs {
 // asks for the geometry a launch of the problem alone would get (svoh_sparse_align_geometry_key / _enqueue_keyed).
 struct AlignGeometry {
   int cluster_g = 0;       // 0: one workgroup per problem; >= 2: that many co-resident workgroups per problem
-  int nt = 256;            // 256 / 512 threads
+  int nt = 256;            // 128 / 256 / 512 threads
   int rows = 1;            // lanes per patch (1, 2, 4, 8)
   bool latency = false;    // the one-wave-per-SIMD build of the 256-thread kernel
   bool rig = false;        // the build that runs a rig's cameras side by side
-  int32_t key() const { return (1 << 30) | (cluster_g & 0xff) | ((nt == 512 ? 1 : 0) << 8) | ((rows & 0xf) << 9) | ((latency ? 1 : 0) << 13) | ((rig ? 1 : 0) << 14); }
+  int32_t key() const { return (1 << 30) | (cluster_g & 0xff) | ((nt == 512 ? 1 : 0) << 8) | ((rows & 0xf) << 9) | ((latency ? 1 : 0) << 13) | ((rig ? 1 : 0) << 14) | ((nt == 128 ? 1 : 0) << 15); }
   static bool from_key(int32_t k, AlignGeometry* g)
   {
-    if (!(k & (1 << 30)) || (k & ~((1 << 30) | 0x7fff))) return false;
-    g->cluster_g = k & 0xff; g->nt = (k >> 8) & 1 ? 512 : 256; g->rows = (k >> 9) & 0xf; g->latency = (k >> 13) & 1; g->rig = (k >> 14) & 1;
+    if (!(k & (1 << 30)) || (k & ~((1 << 30) | 0xffff))) return false;
+    if (((k >> 15) & 1) && (k & 0x7fff) != 0x0200) return false;   // 128 threads: a lane per patch and nothing else
+    g->cluster_g = k & 0xff; g->nt = (k >> 15) & 1 ? 128 : (k >> 8) & 1 ? 512 : 256; g->rows = (k >> 9) & 0xf; g->latency = (k >> 13) & 1; g->rig = (k >> 14) & 1;
     return (g->rows == 1 || g->rows == 2 || g->rows == 4 || g->rows == 8) && g->cluster_g != 1 && g->cluster_g <= kClusterMaxWorkgroups;
   }
 };
@@ -2179,10 +2241,17 @@ static AlignGeometry decide_geometry(const svoh_ctx* ctx, const svoh_align_optio
   if (rows != 2 && rows != 4 && rows != 8) rows = 1;
   if (rows > opt->patch_size || cluster) rows = 1;
   if (rows > 1) nt = 512;
+  // Four 128-thread workgroups per compute unit ("Four workgroups per compute unit"): the same eight waves, but a
+  // problem's latency-bound phases (base phase, level set-up, reductions, the step) weigh half as much against its passes, so the
+  // SIMDs stand idle less.  Single-camera problems with 4x4 patches (8x8 patches lose 3 % there), kAlign128MinRounds rounds
+  // of four per compute unit or more.  SVOH_ALIGN_THREADS=128 asks for it at any size, =256 keeps the two-workgroup build.
+  const bool can_128 = !cluster && !z.have_rig;
+  if (can_128 && nt == 256 && opt->patch_size == 4 && n_desc >= kAlign128MinRounds * 4 * ctx->num_cus) nt = 128;
   nt = SvohKnobs::or_default(ctx->knobs.align_threads, nt);
   if (cluster) nt = 256;   // one workgroup per CU at most: all of them are resident together
-  if (nt != 256 && nt != 512) nt = 256;
-  if (nt == 256) rows = 1;
+  if (nt == 128 && !can_128) nt = 256;
+  if (nt != 128 && nt != 256 && nt != 512) nt = 256;
+  if (nt != 512) rows = 1;
   g.nt = nt; g.rows = rows;
   // SVOH_ALIGN_LATENCY_BUILD=0 keeps the batch build for small launches too (A/B)
   g.latency = nt == 256 && !cluster && n_desc < ctx->num_cus && SvohKnobs::or_default(ctx->knobs.align_latency_build, 1) != 0;
@@ -2469,7 +2538,7 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   // (0.52 against 0.71 ms per step, 0.96 against 1.17, 2.03 against 2.21, 3.42 against 3.74: profiles/r08_align_overlap_ab.txt).
   const AlignGeometry geo = forced ? *forced : decide_geometry(ctx, opt, n_desc, cluster ? S : 0, shape);
   const int overlap_knob = ctx->knobs.align_overlap;
-  const bool lane_kind = n_desc >= ctx->num_cus && geo.nt == 256 && !geo.latency && !cluster && !split && !forced && eval_level < 0 && n_pos_jobs == 0 &&
+  const bool lane_kind = n_desc >= ctx->num_cus && (geo.nt == 256 || geo.nt == 128) && !geo.latency && !cluster && !split && !forced && eval_level < 0 && n_pos_jobs == 0 &&
                          (overlap_knob == kKnobUnset || overlap_knob != 0);
   if (lane_kind) SVOH_HIP_TRY(ctx, align_lane_setup(ctx, h_desc.ptr, d_desc.ptr, up_base + up_off));
   const size_t feat_bytes = feat_slots * (kWsPairs * 16 + 2) + 256;
@@ -2616,13 +2685,15 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   // 256 threads: two workgroups per CU, each with <= 29 KB of static LDS (reduction scratch, the 24 KB LDS-DMA staging
   // area of the workspace rows) -> 51 KB for images: levels 4, 3 and 2 of a 640x480 pyramid side by side (50 400 B);
   // launch_one trims the image area to what the instantiation's static LDS really leaves of half a compute unit
-  size_t lds = (nt == 256) ? 52224 : 78 * 1024;
+  // 128 threads: four workgroups per CU, 40 KB each: 15 952 - 16 480 B static (half the staging area) -> 24 480 - 24 576 B for images: levels 4 and 3
+  // side by side (12 000 B) and, when its turn comes, one image of level 2 (19 200 B: the kernel's half-level residency)
+  size_t lds = (nt == 256) ? 52224 : (nt == 128) ? 24576 : 78 * 1024;
   args.latency_build = geo.latency ? 1 : 0;
   args.rig_build = geo.rig ? 1 : 0;
-  args.lds_two_per_cu = (nt == 256 && !cluster && ctx->knobs.align_lds == kKnobUnset && ctx->knobs.align_wg_per_cu == kKnobUnset) ? 1 : 0;
+  args.lds_wg_per_cu = (!cluster && ctx->knobs.align_lds == kKnobUnset && ctx->knobs.align_wg_per_cu == kKnobUnset) ? (nt == 256 ? 2 : nt == 128 ? 4 : 0) : 0;
   lds = (size_t)SvohKnobs::or_default(ctx->knobs.align_lds, (int)lds) & ~(size_t)15;   // the workspace behind the image area is read through 16-byte loads
   // 160 KB per workgroup minus the kernel's static LDS
-  const size_t lds_cap = (nt == 256) ? 163840 - 32768 : 153856;
+  const size_t lds_cap = (nt == 256 || nt == 128) ? 163840 - 32768 : 153856;
   if (lds > lds_cap) lds = lds_cap;
   // a small problem's feature workspace in LDS, behind the image area (512-thread geometry: 78 KB hold the 50 KB of the
   // levels 4..2 of a 640x480 pair and 16 KB of rows; the next finer level would not fit either way)
@@ -2633,8 +2704,8 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   args.lds_img_bytes = (int32_t)(lds - (size_t)args.ws_lds_bytes);   // the launch still asks for all of `lds`
 
   const bool illum = opt->estimate_illumination_gain || opt->estimate_illumination_offset;
-  // resident workgroups per CU: 256-thread groups at 256 VGPRs -> 2; larger groups -> 1
-  int grid = ctx->num_cus * SvohKnobs::or_default(ctx->knobs.align_wg_per_cu, nt == 256 ? 2 : 1);
+  // resident workgroups per CU: 256-thread groups at 256 VGPRs -> 2, 128-thread groups -> 4; larger groups -> 1
+  int grid = ctx->num_cus * SvohKnobs::or_default(ctx->knobs.align_wg_per_cu, nt == 256 ? 2 : nt == 128 ? 4 : 1);
   if (grid > n_desc || grid <= 0) grid = n_desc;
   if (cluster) grid = n_desc;
   args.one_each = 0;   // (not read: see AlignKernelArgs)

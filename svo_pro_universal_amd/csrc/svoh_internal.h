@@ -196,7 +196,7 @@ struct SvohKnobs {
   // (a member of every build: libsvo_hip_testhooks.so links translation units compiled with and without SVOH_TEST_HOOKS, and all
   // of them must agree on where the members behind this one lie; only the test-hook build ever sets or reads it)
   int align_cluster_test_absent = kKnobUnset; // SVOH_ALIGN_CLUSTER_TEST_ABSENT: a partner that never arrives (libsvo_hip_testhooks.so only)
-  int align_threads = kKnobUnset;             // SVOH_ALIGN_THREADS: 256 / 512 (anything else = 256)
+  int align_threads = kKnobUnset;             // SVOH_ALIGN_THREADS: 128 / 256 / 512 (anything else = 256; 128: single-camera problems outside cluster mode)
   int align_rows = kKnobUnset;                // SVOH_ALIGN_ROWS: lanes per patch of the alignment's 512-thread geometry: 2, 4 or 8 (<= patch size); anything else = a lane per patch
   int align_latency_build = kKnobUnset;       // SVOH_ALIGN_LATENCY_BUILD: 0 = small launches use the batch build of the 256-thread kernel too
   int align_lds = kKnobUnset;                 // SVOH_ALIGN_LDS: bytes of LDS for image levels (rounded down to a multiple of 16)

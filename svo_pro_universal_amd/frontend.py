@@ -240,7 +240,7 @@ class Context(object):
         key, grid, n_desc = C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self.lib.svoh_sparse_align_last_launch_info(self.h, C.byref(key), C.byref(grid), C.byref(n_desc)))
         k = key.value
-        return dict(key=k, cluster_g=k & 0xff, nt=512 if (k >> 8) & 1 else 256, rows=(k >> 9) & 0xf,
+        return dict(key=k, cluster_g=k & 0xff, nt=128 if (k >> 15) & 1 else 512 if (k >> 8) & 1 else 256, rows=(k >> 9) & 0xf,
                     latency=bool((k >> 13) & 1), rig=bool((k >> 14) & 1), grid=grid.value, n_desc=n_desc.value)
 
     def last_align_lane(self):
