@@ -613,7 +613,12 @@ typedef struct svoh_feature_batch {
  * depth: n reference depths; px_cur: 2 x n, in = projection estimate, out = match;
  * outputs per feature: result (svoh_match_result), f_cur (3 x n, normalised bearing),
  * search_level, h_inv (align1D only), A_cur_ref (4 x n, col-major 2x2).  Optional
- * outputs may be NULL.  The caller replays the sequential grid-occupancy logic. */
+ * outputs may be NULL.  The caller replays the sequential grid-occupancy logic.
+ * Cameras: a blocking batch of host arrays (SVOH_MEM_HOST, outside a deferred section) may have EQUIDISTANT or ATAN
+ * views; the launch then runs match_direct_wide_kernel with one lane per unit whatever its size and SVOH_MATCHER_G8
+ * say, also for the NONE / RADTAN views beside them.  An ATAN view whose s = d[0] is zero or not finite is
+ * SVOH_ERR_INVALID_ARGUMENT.  Staged, deferred and device-resident batches refuse a wide view: SVOH_ERR_UNSUPPORTED,
+ * nothing touched. */
 int svoh_match_direct_batch(svoh_ctx* ctx, const svoh_matcher_options* options,
                             int n_ref_frames, const svoh_frame_view* ref_frames,
                             const svoh_frame_view* cur_frame, const svoh_feature_batch* features,
@@ -625,7 +630,7 @@ int svoh_match_direct_batch(svoh_ctx* ctx, const svoh_matcher_options* options,
  * which needs the landmark's position: landmark_xyz = 3 x n, world frame (ref_ftr.landmark->pos()), in the memory
  * space of the batch.  A_cur_ref and search_level are those of the affine warp, as in the reference.  Nothing in the
  * reference clears the flag; the branch is built for completeness and runs one lane per feature at every batch size.
- * Not allowed inside a deferred section. */
+ * Not allowed inside a deferred section.  Wide cameras as in svoh_match_direct_batch: host arrays only. */
 int svoh_match_direct_batch_pixelwise(svoh_ctx* ctx, const svoh_matcher_options* options, int n_ref_frames,
                                       const svoh_frame_view* ref_frames, const svoh_frame_view* cur_frame,
                                       const svoh_feature_batch* features, const double* depth, const double* landmark_xyz,
@@ -796,7 +801,12 @@ typedef struct svoh_depth_filter_options {
  * state: 4 x n [mu = 1/depth, sigma2, a, b] (invmu_sigma2_a_b_vec_), updated in place;
  * features->type updated in place (converged / outlier); success[i] = return value of
  * updateSeed; match_result (may be NULL) = svoh_match_result of the epipolar search.
- * Returns the number of successes in *n_success. */
+ * Returns the number of successes in *n_success.
+ * Cameras: a blocking batch of host arrays (SVOH_MEM_HOST, outside a deferred section) may have EQUIDISTANT or ATAN
+ * views; the launch then runs update_seeds_wide_kernel with eight lanes per unit whatever its size and
+ * SVOH_MATCHER_G8 say, also for the NONE / RADTAN views beside them.  An ATAN view whose s = d[0] is zero or not finite
+ * is SVOH_ERR_INVALID_ARGUMENT.  Staged, deferred and device-resident batches, svoh_update_seeds_batch_ex and
+ * svoh_update_seeds_chain refuse a wide view: SVOH_ERR_UNSUPPORTED, nothing touched. */
 int svoh_update_seeds_batch(svoh_ctx* ctx, const svoh_matcher_options* matcher_options,
                             const svoh_depth_filter_options* options,
                             int n_ref_frames, const svoh_frame_view* ref_frames,
@@ -820,7 +830,8 @@ typedef struct svoh_seed_match_outputs {
  * be NULL = svoh_update_seeds_batch).  Entries of seeds whose update returned before the
  * epipolar search (match_result SVOH_MATCH_NOT_RUN) read back as zeros from a host-resident
  * batch.  In a device-resident batch they are unspecified: the per-unit kernels (batches of up to
- * 49 152 seeds) write zeros there as well, the packed kernel of larger batches leaves them untouched. */
+ * 49 152 seeds) write zeros there as well, the packed kernel of larger batches leaves them untouched.
+ * NONE / RADTAN views only: a wide view is SVOH_ERR_UNSUPPORTED in every memory space. */
 int svoh_update_seeds_batch_ex(svoh_ctx* ctx, const svoh_matcher_options* matcher_options,
                                const svoh_depth_filter_options* options,
                                int n_ref_frames, const svoh_frame_view* ref_frames,
@@ -844,7 +855,7 @@ int svoh_update_seeds_batch_ex(svoh_ctx* ctx, const svoh_matcher_options* matche
  * beyond a unit's chain.  max_steps is read only when one of the two is given.
  * Refused before anything is staged, the context staying usable: chain_begin not non-decreasing from 0, a chain_idx
  * outside [0, n_chain_frames), an unknown frame handle (SVOH_ERR_BAD_HANDLE), a camera that is not the frame's size, a
- * wide distortion model (SVOH_ERR_UNSUPPORTED), max_steps smaller than the longest chain while step outputs are asked for.
+ * wide distortion model (SVOH_ERR_UNSUPPORTED: the chain has no wide twin, unlike svoh_update_seeds_batch), max_steps smaller than the longest chain while step outputs are asked for.
  * n == 0 or no chain entries at all: SVOH_OK without a launch, zeros (SVOH_MATCH_NOT_RUN) in the outputs.
  * The call blocks.  It stages through buffers of its own: like svoh_epipolar_match_batch it is allowed inside an open
  * deferred section, also while a flushed seed batch is in flight, and leaves the section's batches intact.  Small
@@ -884,7 +895,11 @@ typedef struct svoh_epipolar_match_outputs {
  * overload, matcher.cpp:143-155).
  * d_inv_common = {d_estimate_inv, d_min_inv, d_max_inv} for every feature; d_inv (3 x n, may be NULL, lives
  * where features->mem_space says) overrides it per feature.
- * The caller replays its own sequential bookkeeping (the stereo loop stops at n_desired successes). */
+ * The caller replays its own sequential bookkeeping (the stereo loop stops at n_desired successes).
+ * Cameras: a batch of host arrays (SVOH_MEM_HOST) may have EQUIDISTANT or ATAN views; the launch then runs
+ * epipolar_match_wide_kernel with one wave per unit whatever its size and SVOH_MATCHER_G8 say, also for the NONE /
+ * RADTAN views beside them.  An ATAN view whose s = d[0] is zero or not finite is SVOH_ERR_INVALID_ARGUMENT.  A
+ * device-resident batch refuses a wide view: SVOH_ERR_UNSUPPORTED. */
 int svoh_epipolar_match_batch(svoh_ctx* ctx, const svoh_matcher_options* options,
                               int n_ref_frames, const svoh_frame_view* ref_frames,
                               const svoh_frame_view* cur_frame, const svoh_se3* T_cur_ref,

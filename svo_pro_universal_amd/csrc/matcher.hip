@@ -31,9 +31,13 @@
 
 namespace svoh {
 
-struct DevFrameView {
+// One layout for both camera families: DevFrameView (CamModel) is what every launch without a wide camera reads, as it always
+// did; DevFrameViewWide (CamModelWide) is the *_wide_kernel twins' (DESIGN.md 4).  The device functions below take the view type
+// as a template parameter and so evaluate project3 / back_project3 of the view's own camera type.
+template <class Cam>
+struct DevFrameViewT {
   DevImage lv[SVOH_MAX_LEVELS];
-  CamModel cam;
+  Cam cam;
   Rigid T_f_w;
   double seed_mu_range;
   int32_t n_levels;
@@ -46,6 +50,8 @@ struct DevFrameView {
   // SVOH_BATCH_WHOLE_SETS: the batch's units [unit_begin, unit_begin + feat_n) are this reference frame's features 0 .. feat_n - 1
   int32_t unit_begin;
 };
+struct DevFrameView : DevFrameViewT<CamModel> {};
+struct DevFrameViewWide : DevFrameViewT<CamModelWide> {};
 
 // SVOH_BATCH_WHOLE_SETS: the reference frame whose units hold unit / slot p = the last one that begins at or before p
 __device__ __forceinline__ int whole_sets_frame_of(const DevFrameView* ref_frames, int n_ref, int p, int n = 0)
@@ -61,9 +67,10 @@ __device__ __forceinline__ int whole_sets_frame_of(const DevFrameView* ref_frame
   return lo;
 }
 
-struct MatcherArgs {
-  const DevFrameView* ref_frames;
-  const DevFrameView* cur_frame;
+template <class View>
+struct MatcherArgsT {
+  const View* ref_frames;
+  const View* cur_frame;
   svoh_matcher_options mopt;
   svoh_depth_filter_options dopt;
   int n;
@@ -97,12 +104,15 @@ struct MatcherArgs {
   // kernel, which walks the reference frames' tile-ordered columns; the other geometries get them filled in by the prologue
   int whole_sets;
 };
+struct MatcherArgs : MatcherArgsT<DevFrameView> {};
+struct MatcherArgsWide : MatcherArgsT<DevFrameViewWide> {};   // differs in the type the first two members point to, in nothing else
 
 constexpr int kPwbStride = 100;
 constexpr int kG8MaxUnits = 49152;   // up to here a launch uses eight lanes per unit (measured crossover)
 
 // indices of feature i are usable (always true for host-resident batches, which the host validates)
-__device__ __forceinline__ bool feature_indices_ok(const MatcherArgs& a, int i)
+template <class Args>
+__device__ __forceinline__ bool feature_indices_ok(const Args& a, int i)
 {
   const int ri = a.ref_frame_idx[i];
   if ((unsigned)ri >= (unsigned)a.n_ref_frames) return false;
@@ -196,7 +206,8 @@ __device__ __forceinline__ bool is_edgelet(int t)
 }
 
 // patch_warp.cpp:20-60 (pinhole cameras)
-__device__ void get_warp_matrix_affine(const CamModel& cam_ref, const CamModel& cam_cur, double pxr, double pyr,
+template <class Cam>
+__device__ void get_warp_matrix_affine(const Cam& cam_ref, const Cam& cam_cur, double pxr, double pyr,
                                        const Vec3& f_ref, double depth_ref, const Rigid& T_cur_ref, int level_ref,
                                        double A[4])
 {
@@ -293,7 +304,8 @@ __device__ bool warp_affine(const double A_cur_ref[4], const DevImage& img_ref, 
 // pixel of the 10x10 patch (search level of the current frame) is back-projected to the landmark's distance from the
 // current camera, carried into the reference frame and sampled in the reference level.  One lane per unit: nothing in
 // the reference clears the flag, the branch exists for completeness (svoh_match_direct_batch_pixelwise).
-__device__ bool warp_pixelwise(const DevFrameView& cur_frame, const DevFrameView& ref_frame, double pxr, double pyr,
+template <class View>
+__device__ bool warp_pixelwise(const View& cur_frame, const View& ref_frame, double pxr, double pyr,
                                const Vec3& landmark, int level_ref, int level_cur, unsigned char* patch)
 {
   constexpr int halfpatch_size = 5;
@@ -1241,15 +1253,16 @@ __device__ bool warp_affine_packed(const double A_cur_ref[4], const DevImage& im
   return true;
 }
 
-__device__ __forceinline__ Rigid T_cur_ref_of(const DevFrameView& ref, const DevFrameView& cur)
+template <class View>
+__device__ __forceinline__ Rigid T_cur_ref_of(const View& ref, const View& cur)
 {
   return mul(cur.T_f_w, inverse(ref.T_f_w));
 }
 
 // matcher.cpp:31-141
-template <bool G8 = false>
-__device__ int find_match_direct(MatcherState& m, const svoh_matcher_options& opt, const DevFrameView& ref_frame,
-                                 const DevFrameView& cur_frame, double pxr, double pyr, const Vec3& f_ref, double gx,
+template <bool G8 = false, class View>
+__device__ int find_match_direct(MatcherState& m, const svoh_matcher_options& opt, const View& ref_frame,
+                                 const View& cur_frame, double pxr, double pyr, const Vec3& f_ref, double gx,
                                  double gy, int level, int type, double ref_depth, double& pcx, double& pcy,
                                  const double* landmark = nullptr /* one lane per unit only: the pixelwise warp */)
 {
@@ -1296,7 +1309,8 @@ __device__ int find_match_direct(MatcherState& m, const svoh_matcher_options& op
   return SVOH_MATCH_SUCCESS;
 }
 
-__device__ __forceinline__ bool is_patch_within_image(const DevFrameView& frame, int px, int py, int patch_level)
+template <class View>
+__device__ __forceinline__ bool is_patch_within_image(const View& frame, int px, int py, int patch_level)
 {
   constexpr int kPatchSize = 8;
   return !(px < kPatchSize || py < kPatchSize || px >= ((int)(frame.cam.width / (1 << patch_level)) - kPatchSize) ||
@@ -1304,8 +1318,8 @@ __device__ __forceinline__ bool is_patch_within_image(const DevFrameView& frame,
 }
 
 // G: 0 = one lane per unit, 1 = eight lanes per unit, 2 = packed (one lane per unit in this phase, packed template)
-template <int G8>
-__device__ __forceinline__ bool update_zmssd(const DevFrameView& frame, int px, int py, int patch_level,
+template <int G8, class View>
+__device__ __forceinline__ bool update_zmssd(const View& frame, int px, int py, int patch_level,
                                              const MatcherState& m, int sumA, int sumAA, int& zmssd_best)
 {
   const DevImage& im = frame.lv[patch_level];
@@ -1319,8 +1333,8 @@ __device__ __forceinline__ bool update_zmssd(const DevFrameView& frame, int px, 
 }
 
 // matcher.cpp:340-413
-template <int G8>
-__device__ void scan_epipolar_unit_plane(MatcherState& m, const svoh_matcher_options& opt, const DevFrameView& frame,
+template <int G8, class View>
+__device__ void scan_epipolar_unit_plane(MatcherState& m, const svoh_matcher_options& opt, const View& frame,
                                          const Vec3& A, const Vec3& B, const Vec3& C, int patch_level, int sumA, int sumAA,
                                          double& bx, double& by, int& zmssd_best)
 {
@@ -1470,8 +1484,8 @@ __device__ Vec3 angle_axis_rotate(const Vec3& axis, double angle, const Vec3& v)
 }
 
 // matcher.cpp:415-488
-template <int G8>
-__device__ void scan_epipolar_unit_sphere(MatcherState& m, const svoh_matcher_options& opt, const DevFrameView& frame,
+template <int G8, class View>
+__device__ void scan_epipolar_unit_sphere(MatcherState& m, const svoh_matcher_options& opt, const View& frame,
                                           const Vec3& A, const Vec3& B, const Vec3& C, int patch_level, int sumA, int sumAA,
                                           double& bx, double& by, int& zmssd_best)
 {
@@ -1618,7 +1632,8 @@ __device__ __forceinline__ W64Round w64_round(bool valid, bool within, int pxi0,
   return r;
 }
 
-__device__ void scan_epipolar_unit_sphere_w64(MatcherState& m, const svoh_matcher_options& opt, const DevFrameView& frame,
+template <class View>
+__device__ void scan_epipolar_unit_sphere_w64(MatcherState& m, const svoh_matcher_options& opt, const View& frame,
                                               const Vec3& A, const Vec3& B, const Vec3& C, int patch_level, int sumA, int sumAA,
                                               double& bx, double& by, int& zmssd_best)
 {
@@ -1673,7 +1688,8 @@ __device__ void scan_epipolar_unit_sphere_w64(MatcherState& m, const svoh_matche
   project3(frame.cam, f_best, bx, by);
 }
 
-__device__ void scan_epipolar_unit_plane_w64(MatcherState& m, const svoh_matcher_options& opt, const DevFrameView& frame,
+template <class View>
+__device__ void scan_epipolar_unit_plane_w64(MatcherState& m, const svoh_matcher_options& opt, const View& frame,
                                              const Vec3& A, const Vec3& B, const Vec3& C, int patch_level, int sumA, int sumAA,
                                              double& bx, double& by, int& zmssd_best)
 {
@@ -1762,9 +1778,9 @@ __device__ int depth_from_triangulation(const Rigid& T_search_ref, const Vec3& f
 // ZMSSD scan.  Returns a final result code, or kMatchRefinePending (m.px_cur = start of the refinement at level 0,
 // m.epi_dir = its 1-D direction) / kMatchTriangulatePending (no refinement wanted).
 constexpr int kMatchRefinePending = -1000, kMatchTriangulatePending = -1001;
-template <int G8 = 0>
-__device__ int epipolar_match_search(MatcherState& m, const svoh_matcher_options& opt, const DevFrameView& ref_frame,
-                                     const DevFrameView& cur_frame, const Rigid& T_cur_ref, double pxr, double pyr,
+template <int G8 = 0, class View>
+__device__ int epipolar_match_search(MatcherState& m, const svoh_matcher_options& opt, const View& ref_frame,
+                                     const View& cur_frame, const Rigid& T_cur_ref, double pxr, double pyr,
                                      const Vec3& f_ref, double gx, double gy, int level, int type,
                                      double d_estimate_inv, double d_min_inv, double d_max_inv)
 {
@@ -1849,7 +1865,8 @@ __device__ int epipolar_match_search(MatcherState& m, const svoh_matcher_options
 
 // The rest of Matcher::findEpipolarMatchDirect once the refinement (if any) has run: matcher.cpp:262-289 tail,
 // :216-219 / :236-239.  aligned = return value of align1D / align2D, (sx, sy) = its result at the search level.
-__device__ int epipolar_match_finish(MatcherState& m, const DevFrameView& cur_frame, const Rigid& T_cur_ref, const Vec3& f_ref,
+template <class View>
+__device__ int epipolar_match_finish(MatcherState& m, const View& cur_frame, const Rigid& T_cur_ref, const Vec3& f_ref,
                                      bool refined, bool aligned, double sx, double sy, double& depth)
 {
   if (refined) {
@@ -1864,9 +1881,9 @@ __device__ int epipolar_match_finish(MatcherState& m, const DevFrameView& cur_fr
 
 // Matcher::findEpipolarMatchDirect in one piece.  G8: 0 one lane per unit, 1 eight lanes per unit, 3 one wave per unit
 // (the search of geometry 3, the refinement by its eight-lane groups, all of which compute the same)
-template <int G8 = 0>
-__device__ int find_epipolar_match_direct(MatcherState& m, const svoh_matcher_options& opt, const DevFrameView& ref_frame,
-                                          const DevFrameView& cur_frame, const Rigid& T_cur_ref, double pxr, double pyr,
+template <int G8 = 0, class View>
+__device__ int find_epipolar_match_direct(MatcherState& m, const svoh_matcher_options& opt, const View& ref_frame,
+                                          const View& cur_frame, const Rigid& T_cur_ref, double pxr, double pyr,
                                           const Vec3& f_ref, double gx, double gy, int level, int type,
                                           double d_estimate_inv, double d_min_inv, double d_max_inv, double& depth)
 {
@@ -1969,8 +1986,8 @@ __device__ __forceinline__ void flush_counters(unsigned int* c, int i, const Mat
 }
 
 // G8: eight lanes per unit (small batches, see g8_sum): unit = threadIdx.x / 8, the lane's patch row = threadIdx.x % 8
-template <bool G8>
-__device__ __forceinline__ void match_direct_body(const MatcherArgs& a, int block, unsigned char* s_pwb)
+template <bool G8, class Args>
+__device__ __forceinline__ void match_direct_body(const Args& a, int block, unsigned char* s_pwb)
 {
   const int unit = G8 ? (int)(threadIdx.x >> 3) : (int)threadIdx.x;
   const int i = block * (G8 ? 8 : 64) + unit;
@@ -1994,10 +2011,10 @@ __device__ __forceinline__ void match_direct_body(const MatcherArgs& a, int bloc
   m.n_warp = 0; m.n_zmssd = 0; m.n_align_it = 0;
   m.A[0] = m.A[1] = m.A[2] = m.A[3] = 0.0;
   m.f_cur = { 0.0, 0.0, 0.0 };
-  const DevFrameView& ref = a.ref_frames[a.ref_frame_idx[i]];
+  const auto& ref = a.ref_frames[a.ref_frame_idx[i]];
   const Vec3 f = { a.f[3 * i], a.f[3 * i + 1], a.f[3 * i + 2] };
   double pcx = a.px_cur[2 * i], pcy = a.px_cur[2 * i + 1];
-  const DevFrameView& curf = a.cur_frame[a.cur_frame_idx ? a.cur_frame_idx[i] : 0];
+  const auto& curf = a.cur_frame[a.cur_frame_idx ? a.cur_frame_idx[i] : 0];
   const int r = find_match_direct<G8>(m, a.mopt, ref, curf, a.px[2 * i], a.px[2 * i + 1], f, a.grad[2 * i],
                                       a.grad[2 * i + 1], a.level[i], a.type[i], a.depth[i], pcx, pcy,
                                       (!G8 && a.landmark_xyz) ? &a.landmark_xyz[3 * i] : nullptr);
@@ -2017,6 +2034,14 @@ __global__ __launch_bounds__(64) void match_direct_kernel(const MatcherArgs a)
   __shared__ __attribute__((aligned(16))) unsigned char s_pwb[64 * kPwbStride];
   match_direct_body<G8>(a, (int)blockIdx.x, s_pwb);
 }
+// the twin for a launch with a wide camera among its views: instantiated with one lane per unit only, the
+// geometry that has both warps
+template <bool G8>
+__global__ __launch_bounds__(64) void match_direct_wide_kernel(const MatcherArgsWide a)
+{
+  __shared__ __attribute__((aligned(16))) unsigned char s_pwb[64 * kPwbStride];
+  match_direct_body<G8>(a, (int)blockIdx.x, s_pwb);
+}
 
 // ---- depth_filter_utils::updateSeed (depth_filter.cpp:367-499): gate, apply and the step built from them ----------------
 // a seed's convergence threshold on sigma2 (depth_filter.cpp:371-376)
@@ -2028,7 +2053,8 @@ __device__ __forceinline__ double seed_convergence_thresh(const svoh_depth_filte
 
 // The gate: everything updateSeed checks before it calls the matcher, in two halves with T_cur_ref between them.
 // First the seed's type and the frames: isSeed, the frame itself, outliers, converged seeds under check_convergence.
-__device__ __forceinline__ bool seed_gate_type(const svoh_depth_filter_options& dopt, const DevFrameView& ref, const DevFrameView& cur, int type)
+template <class View>
+__device__ __forceinline__ bool seed_gate_type(const svoh_depth_filter_options& dopt, const View& ref, const View& cur, int type)
 {
   if (!(type < 6)) return false;  // isSeed
   if (cur.id == ref.id) return false;
@@ -2041,7 +2067,8 @@ __device__ __forceinline__ bool seed_gate_type(const svoh_depth_filter_options& 
 
 // ... then the projection into the current image and its 9-pixel border.  state / f: the seed's four and three doubles, in
 // memory or in registers.
-__device__ __forceinline__ bool seed_gate_visible(const svoh_depth_filter_options& dopt, const DevFrameView& cur, const Rigid& T_cur_ref,
+template <class View>
+__device__ __forceinline__ bool seed_gate_visible(const svoh_depth_filter_options& dopt, const View& cur, const Rigid& T_cur_ref,
                                                   const double* state, const double* f)
 {
   if (!dopt.check_visibility) return true;
@@ -2056,7 +2083,8 @@ __device__ __forceinline__ bool seed_gate_visible(const svoh_depth_filter_option
 }
 
 // The whole gate; T_cur_ref comes out for the search and for seed_update_apply.
-__device__ __forceinline__ bool seed_update_gate(const svoh_depth_filter_options& dopt, const DevFrameView& ref, const DevFrameView& cur,
+template <class View>
+__device__ __forceinline__ bool seed_update_gate(const svoh_depth_filter_options& dopt, const View& ref, const View& cur,
                                                  int type, const double* state, const double* f, Rigid& T_cur_ref)
 {
   if (!seed_gate_type(dopt, ref, cur, type)) return false;
@@ -2067,7 +2095,8 @@ __device__ __forceinline__ bool seed_update_gate(const svoh_depth_filter_options
 // After a successful match at `depth`: tau, the filter update, the outlier mark and the promotion to *_CONVERGED against
 // seed_mu_range / cur_thresh (seed_convergence_thresh of the type the seed had before).
 // Returns updateSeed's value; st is what the filter left in either case.
-__device__ __forceinline__ bool seed_update_apply(const svoh_depth_filter_options& dopt, const DevFrameView& ref, const Rigid& T_cur_ref,
+template <class View>
+__device__ __forceinline__ bool seed_update_apply(const svoh_depth_filter_options& dopt, const View& ref, const Rigid& T_cur_ref,
                                                   const Vec3& f, double depth, double cur_thresh, double (&st)[4], int& type)
 {
   const double depth_sigma = compute_tau(inverse(T_cur_ref), f, depth, dopt.px_error_angle);
@@ -2115,8 +2144,8 @@ __device__ __forceinline__ bool seed_update_step(const MatcherArgs& a, MatcherSt
 // DepthFilter::updateSeeds (depth_filter.cpp:200-233): gate, search and apply per unit, state and type in memory.  Only the
 // reporting lane goes on behind the search, so the step is spelled out here, not seed_update_step (which every lane runs through)
 // G8: 0 one lane per unit, 1 eight lanes per unit, 3 one wave per unit (scan 64 steps at a time)
-template <int G8>
-__device__ __forceinline__ void update_seeds_body(const MatcherArgs& a, int block, unsigned char* s_pwb)
+template <int G8, class Args>
+__device__ __forceinline__ void update_seeds_body(const Args& a, int block, unsigned char* s_pwb)
 {
   const UnitOfThread u = unit_of_thread<G8>(block);
   const int i = u.i;
@@ -2134,8 +2163,8 @@ __device__ __forceinline__ void update_seeds_body(const MatcherArgs& a, int bloc
   }
   if (!feature_indices_ok(a, i)) return;
   const int type0 = a.type[i];
-  const DevFrameView& ref = a.ref_frames[a.ref_frame_idx[i]];
-  const DevFrameView& cur = a.cur_frame[a.cur_frame_idx ? a.cur_frame_idx[i] : 0];
+  const auto& ref = a.ref_frames[a.ref_frame_idx[i]];
+  const auto& cur = a.cur_frame[a.cur_frame_idx ? a.cur_frame_idx[i] : 0];
   const double cur_thresh = seed_convergence_thresh(a.dopt, type0);
   // (the gate's halves with T_cur_ref computed ahead of both: between them, as in seed_update_gate, update_seeds_kernel<3>
   // spills an SGPR it did not spill before; profiles/matcher_refactor_resources.txt)
@@ -2176,6 +2205,13 @@ __device__ __forceinline__ void update_seeds_body(const MatcherArgs& a, int bloc
 
 template <int G8>
 __global__ __launch_bounds__(64) void update_seeds_kernel(const MatcherArgs a)
+{
+  __shared__ __attribute__((aligned(16))) unsigned char s_pwb[64 * kPwbStride];
+  update_seeds_body<G8>(a, (int)blockIdx.x, s_pwb);
+}
+// the wide twin: instantiated with eight lanes per unit only
+template <int G8>
+__global__ __launch_bounds__(64) void update_seeds_wide_kernel(const MatcherArgsWide a)
 {
   __shared__ __attribute__((aligned(16))) unsigned char s_pwb[64 * kPwbStride];
   update_seeds_body<G8>(a, (int)blockIdx.x, s_pwb);
@@ -2661,46 +2697,57 @@ __global__ __launch_bounds__(kPkThreads) __attribute__((amdgpu_waves_per_eu(3)))
 
 // n x Matcher::findEpipolarMatchDirect with an explicit T_cur_ref (matcher.cpp:157-241), align_1d = isEdgelet(type):
 // the call StereoTriangulation::compute makes per new feature (stereo_triangulation.cpp:92-104)
+// (one text for both kernels, as a macro: through a function shared with the twin, epipolar_match_kernel does not disassemble as
+// it did; the other two entries have had such a function all along)
+#define SVOH_EPIPOLAR_MATCH_KERNEL_BODY                                                                                           \
+  __shared__ __attribute__((aligned(16))) unsigned char s_pwb[64 * kPwbStride];                                                   \
+  const UnitOfThread u = unit_of_thread<G8>((int)blockIdx.x);                                                                     \
+  const int i = u.i;                                                                                                              \
+  if (i >= a.n) return;                                                                                                           \
+  const bool reporter = u.reporter;                                                                                               \
+  if (!feature_indices_ok(a, i)) {                                                                                                \
+    if (reporter) {                                                                                                               \
+      a.result[i] = SVOH_MATCH_NOT_RUN;                                                                                           \
+      reinterpret_cast<uint4*>(a.unit_counts)[i] = make_uint4(0u, 0u, 0u, 0u);                                                    \
+    }                                                                                                                             \
+    return;                                                                                                                       \
+  }                                                                                                                               \
+  const int ri = a.ref_frame_idx[i], ci = a.cur_frame_idx ? a.cur_frame_idx[i] : 0;                                               \
+  const auto& ref = a.ref_frames[ri];                                                                                             \
+  const auto& cur = a.cur_frame[ci];                                                                                              \
+  const Rigid T_cur_ref = a.T_cur_ref ? a.T_cur_ref[(size_t)ri * a.n_cur_frames + ci] : T_cur_ref_of(ref, cur);                   \
+  const int type = a.type[i];                                                                                                     \
+  MatcherState m;                                                                                                                 \
+  matcher_state_reset(m, s_pwb + u.unit * kPwbStride, G8 ? (int)(threadIdx.x & 7) : 0, is_edgelet(type));                         \
+  const Vec3 f = { a.f[3 * i], a.f[3 * i + 1], a.f[3 * i + 2] };                                                                  \
+  const double d_est = a.d_inv ? a.d_inv[3 * i] : a.d_inv_common[0];                                                              \
+  const double d_min = a.d_inv ? a.d_inv[3 * i + 1] : a.d_inv_common[1];                                                          \
+  const double d_max = a.d_inv ? a.d_inv[3 * i + 2] : a.d_inv_common[2];                                                          \
+  double depth = 0.0;                                                                                                             \
+  const int res = find_epipolar_match_direct<G8>(m, a.mopt, ref, cur, T_cur_ref, a.px[2 * i], a.px[2 * i + 1], f, a.grad[2 * i],  \
+                                                 a.grad[2 * i + 1], a.level[i], type, d_est, d_min, d_max, depth);                \
+  if (!reporter) return;                                                                                                          \
+  a.result[i] = res;                                                                                                              \
+  a.depth_out[i] = depth;                                                                                                         \
+  if (a.px_cur) { a.px_cur[2 * i] = m.px_cur[0]; a.px_cur[2 * i + 1] = m.px_cur[1]; }                                             \
+  if (a.f_cur) { a.f_cur[3 * i] = m.f_cur.x; a.f_cur[3 * i + 1] = m.f_cur.y; a.f_cur[3 * i + 2] = m.f_cur.z; }                    \
+  if (a.search_level) a.search_level[i] = m.search_level;                                                                         \
+  if (a.h_inv) a.h_inv[i] = m.h_inv;                                                                                              \
+  if (a.A_cur_ref) for (int k = 0; k < 4; ++k) a.A_cur_ref[4 * i + k] = m.A[k];                                                   \
+  flush_counters(a.unit_counts, i, m, res == SVOH_MATCH_SUCCESS ? 1 : 0);
+
 template <int G8>
 __global__ __launch_bounds__(64) void epipolar_match_kernel(const MatcherArgs a)
 {
-  __shared__ __attribute__((aligned(16))) unsigned char s_pwb[64 * kPwbStride];
-  const UnitOfThread u = unit_of_thread<G8>((int)blockIdx.x);
-  const int i = u.i;
-  if (i >= a.n) return;
-  const bool reporter = u.reporter;
-  if (!feature_indices_ok(a, i)) {
-    if (reporter) {
-      a.result[i] = SVOH_MATCH_NOT_RUN;
-      reinterpret_cast<uint4*>(a.unit_counts)[i] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    return;
-  }
-  const int ri = a.ref_frame_idx[i], ci = a.cur_frame_idx ? a.cur_frame_idx[i] : 0;
-  const DevFrameView& ref = a.ref_frames[ri];
-  const DevFrameView& cur = a.cur_frame[ci];
-  const Rigid T_cur_ref = a.T_cur_ref ? a.T_cur_ref[(size_t)ri * a.n_cur_frames + ci] : T_cur_ref_of(ref, cur);
-  const int type = a.type[i];
-  MatcherState m;
-  matcher_state_reset(m, s_pwb + u.unit * kPwbStride, G8 ? (int)(threadIdx.x & 7) : 0, is_edgelet(type));
-  const Vec3 f = { a.f[3 * i], a.f[3 * i + 1], a.f[3 * i + 2] };
-  const double d_est = a.d_inv ? a.d_inv[3 * i] : a.d_inv_common[0];
-  const double d_min = a.d_inv ? a.d_inv[3 * i + 1] : a.d_inv_common[1];
-  const double d_max = a.d_inv ? a.d_inv[3 * i + 2] : a.d_inv_common[2];
-  double depth = 0.0;
-  const int res = find_epipolar_match_direct<G8>(m, a.mopt, ref, cur, T_cur_ref, a.px[2 * i], a.px[2 * i + 1], f, a.grad[2 * i],
-                                                 a.grad[2 * i + 1], a.level[i], type, d_est, d_min, d_max, depth);
-  if (!reporter) return;
-  a.result[i] = res;
-  a.depth_out[i] = depth;
-  if (a.px_cur) { a.px_cur[2 * i] = m.px_cur[0]; a.px_cur[2 * i + 1] = m.px_cur[1]; }
-  if (a.f_cur) { a.f_cur[3 * i] = m.f_cur.x; a.f_cur[3 * i + 1] = m.f_cur.y; a.f_cur[3 * i + 2] = m.f_cur.z; }
-  if (a.search_level) a.search_level[i] = m.search_level;
-  if (a.h_inv) a.h_inv[i] = m.h_inv;
-  if (a.A_cur_ref) for (int k = 0; k < 4; ++k) a.A_cur_ref[4 * i + k] = m.A[k];
-  flush_counters(a.unit_counts, i, m, res == SVOH_MATCH_SUCCESS ? 1 : 0);
+  SVOH_EPIPOLAR_MATCH_KERNEL_BODY
 }
-
+// the wide twin: instantiated with one wave per unit only (the stereo seam's long searches)
+template <int G8>
+__global__ __launch_bounds__(64) void epipolar_match_wide_kernel(const MatcherArgsWide a)
+{
+  SVOH_EPIPOLAR_MATCH_KERNEL_BODY
+}
+#undef SVOH_EPIPOLAR_MATCH_KERNEL_BODY
 
 // The packed geometry for the other two matcher entries (large batches of svoh_match_direct_batch /
 // svoh_epipolar_match_batch): phase A one lane per unit (geometry, affine warp with the corner test and two-tap loads,
@@ -2854,20 +2901,26 @@ __global__ __launch_bounds__(kPkThreads) __attribute__((amdgpu_waves_per_eu(3)))
 // host side
 // ---------------------------------------------------------------------------
 
-static int fill_view(svoh_ctx* ctx, const svoh_frame_view& v, DevFrameView* out, const char* what, bool pose_from_results_allowed = false)
+// wide_allowed: the entry runs EQUIDISTANT | ATAN views (the blocking host-array forms of svoh_update_seeds_batch, svoh_match_direct_batch,
+// svoh_match_direct_batch_pixelwise and svoh_epipolar_match_batch); everything else refuses them, as the default says
+template <class View>
+static int fill_view(svoh_ctx* ctx, const svoh_frame_view& v, View* out, const char* what, bool pose_from_results_allowed = false,
+                     bool wide_allowed = false)
 {
   if (v.pose_result_index_plus1 != 0 && !pose_from_results_allowed)
     return set_error(ctx, SVOH_ERR_INVALID_ARGUMENT, "%s: pose_result_index_plus1 is for the current frames of a staged seed batch queued from the hook of svoh_optimize_pose_batch_hook", what);
   const Frame* f = find_frame(ctx, v.frame);
   if (!f) return set_error(ctx, SVOH_ERR_BAD_HANDLE, "%s: unknown frame handle %llu", what, (unsigned long long)v.frame);
-  if (v.cam.distortion != SVOH_DISTORTION_NONE && v.cam.distortion != SVOH_DISTORTION_RADTAN)
+  if (!camera_is_narrow(v.cam) && !(wide_allowed && camera_is_known(v.cam)))
     return set_error(ctx, SVOH_ERR_UNSUPPORTED, "%s: unsupported distortion model", what);
+  if (v.cam.distortion == SVOH_DISTORTION_ATAN && !(v.cam.d[0] != 0.0 && std::isfinite(v.cam.d[0])))
+    return set_error(ctx, SVOH_ERR_INVALID_ARGUMENT, "%s: ATAN (fisheye) camera: s = d[0] must be finite and non-zero", what);
   // the matcher's bounds tests use the camera's size (matcher.cpp:67-70, 340-413): it must be the frame's
   if (v.cam.width != f->lv[0].w || v.cam.height != f->lv[0].h)
     return set_error(ctx, SVOH_ERR_INVALID_ARGUMENT, "%s: camera is %dx%d but the frame's level 0 is %dx%d", what,
                      v.cam.width, v.cam.height, f->lv[0].w, f->lv[0].h);
   for (int l = 0; l < SVOH_MAX_LEVELS; ++l) out->lv[l] = l < f->n_levels ? f->lv[l] : DevImage{ nullptr, 0, 0, 0, 0 };
-  out->cam = load_camera(v.cam);
+  out->cam = load_camera_as<decltype(out->cam)>(v.cam);
   out->T_f_w = load_rigid(v.T_f_w);
   out->seed_mu_range = v.seed_mu_range;
   out->n_levels = f->n_levels;
@@ -2882,6 +2935,35 @@ static int fill_view(svoh_ctx* ctx, const svoh_frame_view& v, DevFrameView* out,
     out->feat_spx = it->second.spx; out->feat_sf = it->second.sf; out->feat_sgrad = it->second.sgrad; out->feat_slevel = it->second.slevel; out->feat_perm = it->second.perm;
   }
   return SVOH_OK;
+}
+
+// The views of a launch once more for the *_wide_kernel twins, iff one of them has a wide camera (else `wviews` stays empty and
+// the launch runs the kernels it always ran).  After the narrow fill_view of every view has passed with wide_allowed.
+static int fill_wide_views(svoh_ctx* ctx, int n_ref_frames, const svoh_frame_view* ref_frames, int n_cur, const svoh_frame_view* cur_frame,
+                           std::vector<DevFrameViewWide>& wviews)
+{
+  bool wide = false;
+  for (int k = 0; k < n_ref_frames; ++k) wide = wide || !camera_is_narrow(ref_frames[k].cam);
+  for (int k = 0; k < n_cur; ++k) wide = wide || !camera_is_narrow(cur_frame[k].cam);
+  if (!wide) return SVOH_OK;
+  wviews.resize((size_t)n_ref_frames + n_cur);
+  for (int k = 0; k < n_ref_frames + n_cur; ++k) {
+    const int rc = k < n_ref_frames ? fill_view(ctx, ref_frames[k], &wviews[k], "reference frame", false, true)
+                                    : fill_view(ctx, cur_frame[k - n_ref_frames], &wviews[k], "current frame", false, true);
+    if (rc != SVOH_OK) return rc;
+  }
+  return SVOH_OK;
+}
+
+// the same arguments for a twin: `a` with its views staged as DevFrameViewWide
+static MatcherArgsWide widen_args(const MatcherArgs& a)
+{
+  static_assert(sizeof(MatcherArgsWide) == sizeof(MatcherArgs), "MatcherArgsT: the instantiations differ in two pointer types only");
+  MatcherArgsWide w;
+  memcpy(static_cast<void*>(&w), &a, sizeof w);
+  w.ref_frames = reinterpret_cast<const DevFrameViewWide*>(a.ref_frames);
+  w.cur_frame = w.ref_frames + a.n_ref_frames;
+  return w;
 }
 
 struct Staging {
@@ -2908,11 +2990,18 @@ __global__ void count_success_kernel(const uint8_t* success, int n, int* out)
 
 // The kernels of one batch in geometry g8 (0 one lane per unit, 1 eight lanes, 2 packed, 3 one wave per unit), on the
 // context's stream; max_w x max_h = the largest reference frame (bins of the packed seed update).
-static int launch_matcher_kernels(svoh_ctx* ctx, bool seeds, int g8, MatcherArgs& a, int n, int n_ref_frames, int max_w, int max_h)
+// wide: the views are DevFrameViewWide (fill_wide_views) and g8 is the twin's one geometry: eight lanes per unit for the
+// seed update (1), one lane per unit for the direct matcher (0, which has both warps).
+static int launch_matcher_kernels(svoh_ctx* ctx, bool seeds, int g8, MatcherArgs& a, int n, int n_ref_frames, int max_w, int max_h,
+                                  bool wide = false)
 {
   const int units_per_block = g8 == 1 ? 8 : (g8 == 3 ? 1 : 64);
   const dim3 grid((unsigned)((n + units_per_block - 1) / units_per_block)), block(64);
-  if (seeds) {
+  if (wide) {
+    const MatcherArgsWide aw = widen_args(a);
+    if (seeds) hipLaunchKernelGGL(update_seeds_wide_kernel<1>, grid, block, 0, ctx->stream, aw);
+    else hipLaunchKernelGGL(match_direct_wide_kernel<false>, grid, block, 0, ctx->stream, aw);
+  } else if (seeds) {
     if (g8 == 2) {
       if (max_w < 1) max_w = 1;
       if (max_h < 1) max_h = 1;
@@ -2983,7 +3072,7 @@ static int run_matcher(svoh_ctx* ctx, bool seeds, const svoh_matcher_options* mo
                        int n_ref_frames, const svoh_frame_view* ref_frames, const svoh_frame_view* cur_frame,
                        const svoh_feature_batch* fb, const double* depth, double* px_cur, int32_t* result, double* f_cur,
                        int32_t* search_level, double* h_inv, double* A_cur_ref, double* state, uint8_t* success,
-                       int32_t* n_success, const double* landmark_xyz = nullptr)
+                       int32_t* n_success, const double* landmark_xyz = nullptr, bool wide_entry = false)
 {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, mopt && ref_frames && cur_frame && fb && n_ref_frames >= 1, "NULL argument");
@@ -3020,15 +3109,24 @@ static int run_matcher(svoh_ctx* ctx, bool seeds, const svoh_matcher_options* mo
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   SVOH_ALIGN_JOIN(ctx);
 
+  // EQUIDISTANT | ATAN views: the blocking host-array form of an entry that passes wide_entry only (device arrays and a
+  // deferred section keep refusing them, as the staged form does)
+  const bool wide_allowed = wide_entry && !on_device && !ctx->matcher_deferred;
   std::vector<DevFrameView> views((size_t)n_ref_frames + n_cur);
   for (int k = 0; k < n_ref_frames; ++k) {
-    int rc = fill_view(ctx, ref_frames[k], &views[k], "reference frame");
+    int rc = fill_view(ctx, ref_frames[k], &views[k], "reference frame", false, wide_allowed);
     if (rc != SVOH_OK) return rc;
   }
   for (int k = 0; k < n_cur; ++k) {
-    int rc = fill_view(ctx, cur_frame[k], &views[n_ref_frames + k], "current frame");
+    int rc = fill_view(ctx, cur_frame[k], &views[n_ref_frames + k], "current frame", false, wide_allowed);
     if (rc != SVOH_OK) return rc;
   }
+  std::vector<DevFrameViewWide> wviews;
+  {
+    const int rc = fill_wide_views(ctx, n_ref_frames, ref_frames, n_cur, cur_frame, wviews);
+    if (rc != SVOH_OK) return rc;
+  }
+  const bool wide = !wviews.empty();
   if (whole_sets) {
     long long begin = 0;
     for (int k = 0; k < n_ref_frames; ++k) {
@@ -3053,7 +3151,7 @@ static int run_matcher(svoh_ctx* ctx, bool seeds, const svoh_matcher_options* mo
   // [views | inputs | in/out | outputs]; device-resident batches stage the views only
   // and the kernel reads and writes the caller's arrays in place.
   Staging s;
-  const size_t o_views = s.add(views.data(), sizeof(DevFrameView) * views.size());
+  const size_t o_views = wide ? s.add(wviews.data(), sizeof(DevFrameViewWide) * wviews.size()) : s.add(views.data(), sizeof(DevFrameView) * views.size());
   size_t o_idx = 0, o_cidx = 0, o_px = 0, o_f = 0, o_grad = 0, o_level = 0, o_type = 0, o_depth = 0, o_pxcur = 0, o_lm = 0,
          o_state = 0, o_result = 0, o_fcur = 0, o_slevel = 0, o_hinv = 0, o_A = 0, o_success = 0;
   if (!on_device) {
@@ -3106,6 +3204,7 @@ static int run_matcher(svoh_ctx* ctx, bool seeds, const svoh_matcher_options* mo
   if (g8 == 3 && (!seeds || defer)) g8 = 1;   // the direct matcher has no scan
   if (landmark_xyz) g8 = 0;                    // the pixelwise warp exists with one lane per unit only
   if (whole_sets) g8 = 2;                      // (a device batch over whole sets: the packed geometry reads the resident columns itself)
+  if (wide) g8 = seeds ? 1 : 0;                // a wide launch: the twin's one geometry, whatever the size and the knob say
   // Optional outputs of units that return before the matcher runs read back as zeros.  The per-unit kernels write those
   // zeros themselves (match_direct_body, update_seeds_body): a fill of the output block would be one more operation on
   // the stream of every per-frame call (2.6 us each, tools/svoh_call_overhead).  The packed geometry's kernels do not.
@@ -3188,7 +3287,7 @@ static int run_matcher(svoh_ctx* ctx, bool seeds, const svoh_matcher_options* mo
   {
     int max_w = 1, max_h = 1;
     for (int k = 0; k < n_ref_frames; ++k) { max_w = views[k].lv[0].w > max_w ? views[k].lv[0].w : max_w; max_h = views[k].lv[0].h > max_h ? views[k].lv[0].h : max_h; }
-    const int rc = launch_matcher_kernels(ctx, seeds, g8, a, n, n_ref_frames, max_w, max_h);
+    const int rc = launch_matcher_kernels(ctx, seeds, g8, a, n, n_ref_frames, max_w, max_h, wide);
     if (rc != SVOH_OK) return rc;
   }
   if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_stop, ctx->stream));
@@ -3269,16 +3368,23 @@ static int run_epipolar(svoh_ctx* ctx, const svoh_matcher_options* mopt, int n_r
   SVOH_ALIGN_JOIN(ctx);
   std::vector<DevFrameView> views((size_t)n_ref_frames + n_cur);
   int ref_levels = 0;
+  const bool wide_allowed = !on_device;   // EQUIDISTANT | ATAN views: host arrays only
   for (int k = 0; k < n_ref_frames; ++k) {
-    const int rc = fill_view(ctx, ref_frames[k], &views[k], "reference frame");
+    const int rc = fill_view(ctx, ref_frames[k], &views[k], "reference frame", false, wide_allowed);
     if (rc != SVOH_OK) return rc;
     ref_levels = views[k].n_levels > ref_levels ? views[k].n_levels : ref_levels;
   }
   for (int k = 0; k < n_cur; ++k) {
-    const int rc = fill_view(ctx, cur_frame[k], &views[n_ref_frames + k], "current frame");
+    const int rc = fill_view(ctx, cur_frame[k], &views[n_ref_frames + k], "current frame", false, wide_allowed);
     if (rc != SVOH_OK) return rc;
     SVOH_REQUIRE(ctx, views[n_ref_frames + k].n_levels >= ref_levels, "current frame has fewer pyramid levels than a reference frame");
   }
+  std::vector<DevFrameViewWide> wviews;
+  {
+    const int rc = fill_wide_views(ctx, n_ref_frames, ref_frames, n_cur, cur_frame, wviews);
+    if (rc != SVOH_OK) return rc;
+  }
+  const bool wide = !wviews.empty();
   if (!on_device)
     for (int i = 0; i < n; ++i)
       SVOH_REQUIRE(ctx, fb->level[i] < views[fb->ref_frame_idx[i]].n_levels, "feature level beyond the reference pyramid");
@@ -3289,7 +3395,7 @@ static int run_epipolar(svoh_ctx* ctx, const svoh_matcher_options* mopt, int n_r
   }
 
   Staging s;
-  const size_t o_views = s.add(views.data(), sizeof(DevFrameView) * views.size());
+  const size_t o_views = wide ? s.add(wviews.data(), sizeof(DevFrameViewWide) * wviews.size()) : s.add(views.data(), sizeof(DevFrameView) * views.size());
   const size_t o_T = T_cur_ref ? s.add(T.data(), sizeof(Rigid) * T.size()) : 0;
   size_t o_idx = 0, o_cidx = 0, o_px = 0, o_f = 0, o_grad = 0, o_level = 0, o_type = 0, o_dinv = 0;
   if (!on_device) {
@@ -3363,6 +3469,7 @@ static int run_epipolar(svoh_ctx* ctx, const svoh_matcher_options* mopt, int n_r
   int g8 = n <= kG8MaxUnits ? ((mopt->max_epi_search_steps > 128 && n <= kW64MaxUnits) ? 3 : 1) : 2;
   g8 = SvohKnobs::or_default(ctx->knobs.matcher_g8, g8);
   if (g8 < 0 || g8 > 3) g8 = 0;
+  if (wide) g8 = 3;   // a wide launch: the twin's one geometry (one wave per unit), whatever the size and the knob say
   const int units_per_block = g8 == 1 ? 8 : (g8 == 3 ? 1 : 64);
   const dim3 grid((unsigned)((n + units_per_block - 1) / units_per_block)), block(64);
   {
@@ -3372,7 +3479,8 @@ static int run_epipolar(svoh_ctx* ctx, const svoh_matcher_options* mopt, int n_r
     if (rc != SVOH_OK) return rc;
   }
   if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_start, ctx->stream));
-  if (g8 == 2) hipLaunchKernelGGL(match_packed_kernel<false>, dim3((unsigned)((n + kPkThreads - 1) / kPkThreads)), dim3(kPkThreads), 0, ctx->stream, a);
+  if (wide) hipLaunchKernelGGL(epipolar_match_wide_kernel<3>, grid, block, 0, ctx->stream, widen_args(a));
+  else if (g8 == 2) hipLaunchKernelGGL(match_packed_kernel<false>, dim3((unsigned)((n + kPkThreads - 1) / kPkThreads)), dim3(kPkThreads), 0, ctx->stream, a);
   else if (g8 == 3) hipLaunchKernelGGL(epipolar_match_kernel<3>, grid, block, 0, ctx->stream, a);
   else if (g8) hipLaunchKernelGGL(epipolar_match_kernel<1>, grid, block, 0, ctx->stream, a);
   else hipLaunchKernelGGL(epipolar_match_kernel<0>, grid, block, 0, ctx->stream, a);
@@ -4595,7 +4703,7 @@ int svoh_match_direct_batch(svoh_ctx* ctx, const svoh_matcher_options* options, 
                             double* f_cur, int32_t* search_level, double* h_inv, double* A_cur_ref)
 try {
   return run_matcher(ctx, false, options, nullptr, n_ref_frames, ref_frames, cur_frame, features, depth, px_cur, result,
-                     f_cur, search_level, h_inv, A_cur_ref, nullptr, nullptr, nullptr);
+                     f_cur, search_level, h_inv, A_cur_ref, nullptr, nullptr, nullptr, nullptr, true);
 } SVOH_ABI_CATCH(ctx)
 
 int svoh_match_direct_batch_pixelwise(svoh_ctx* ctx, const svoh_matcher_options* options, int n_ref_frames,
@@ -4607,7 +4715,7 @@ try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, landmark_xyz, "landmark_xyz is NULL (svoh_match_direct_batch is the affine warp)");
   return run_matcher(ctx, false, options, nullptr, n_ref_frames, ref_frames, cur_frame, features, depth, px_cur, result,
-                     f_cur, search_level, h_inv, A_cur_ref, nullptr, nullptr, nullptr, landmark_xyz);
+                     f_cur, search_level, h_inv, A_cur_ref, nullptr, nullptr, nullptr, landmark_xyz, true);
 } SVOH_ABI_CATCH(ctx)
 
 int svoh_update_seeds_batch(svoh_ctx* ctx, const svoh_matcher_options* matcher_options,
@@ -4617,7 +4725,7 @@ int svoh_update_seeds_batch(svoh_ctx* ctx, const svoh_matcher_options* matcher_o
                             int32_t* n_success)
 try {
   return run_matcher(ctx, true, matcher_options, options, n_ref_frames, ref_frames, cur_frame, features, nullptr, nullptr,
-                     match_result, nullptr, nullptr, nullptr, nullptr, state, success, n_success);
+                     match_result, nullptr, nullptr, nullptr, nullptr, state, success, n_success, nullptr, true);
 } SVOH_ABI_CATCH(ctx)
 
 int svoh_update_seeds_chain(svoh_ctx* ctx, const svoh_matcher_options* matcher_options, const svoh_depth_filter_options* options,
