@@ -146,8 +146,8 @@ struct AlignKernelArgs {
   //   state: 0 not selected by a-3, 1 selected, 2 selected and visible in the last full pass
   // 16 bytes per lane and pair = one global_load_lds_dwordx4 per pair in the staged patch loop.  The rows of the
   // projection Jacobian (jacobian_proj_cache_, a-4: 96 bytes per feature) are NOT kept: every patch-iteration
-  // rebuilds them from xyz_ref (jac_rows below) -- ~50 fp64 operations against two thirds of the kernel's HBM-side
-  // traffic in round 2 (3.85 of 5.27 GB per 1024 x 2000 launch were these rows read again every iteration)
+  // rebuilds them from xyz_ref, in the camera frame (proj_rows below: ~25 fp64 operations) -- against two thirds of the kernel's
+  // HBM-side traffic in round 2 (3.85 of 5.27 GB per 1024 x 2000 launch were these rows read again every iteration)
   double* wpk;
   int64_t slots;                        // stride of the SoA arrays
   uint8_t* wsel;                        // selected by extractFeaturesSubset (a-3)     } byte masks that only svoh_sparse_align_evaluate reads:
@@ -311,56 +311,57 @@ __device__ __forceinline__ float tukey_weight(float e)
   return 0.0f;
 }
 
-// Per-camera constants of the Jacobian rows, in LDS for the problem's life (21 doubles per camera):
-//   [0..9) R_imu_cam row-major, [9..12) t_imu_cam, [12..21) R_cam_imu row-major
+// Per-camera constants of the Jacobian rows, in LDS for the problem's life:
+//   [0..9) R_imu_cam row-major (camera 0: the Q of the pass's one rotation, rotate_sums), [9..12) tau = R_cam_imu * t_imu_cam,
+//   [12..21) cameras >= 1 of a rig: R_imu_cam(0)^T * R_imu_cam(c), what takes the camera's rows to camera 0's frame
 constexpr int kJacConsts = 24;
 
 // Rows of the projection Jacobian of one feature, scaled to the pyramid level:
 //   a = jp0 * scale, b = jp1 * scale with (jp0; jp1) = Frame::jacobian_xyz2uv_imu (frame.h:342-357) times the focal
 //   length, or Frame::jacobian_xyz2image_imu (frame.cpp:274-290) times -1 (sparse_img_align.cpp:298-309).
 // The reference keeps them per feature (jacobian_proj_cache_); here they are rebuilt from xyz_ref in every
-// patch-iteration (see AlignKernelArgs::wpk).  p_in_cam of the reference is T_cam_imu * (T_imu_cam * xyz_ref):
-// xyz_ref itself up to rounding (the two transformations of a frame are inverses of each other), which is what is
-// used; -x/z is taken as -x * (1/z).  Both are last-bit differences, inside the stated tolerance of H and g.
-__device__ __forceinline__ void jac_rows(const double* jc, const CamModel& cm, bool use_distortion_jac, const Vec3& X,
-                                         double scale, double (&a)[6], double (&b)[6])
+// patch-iteration (see AlignKernelArgs::wpk), and in the CAMERA frame: with alpha, beta the rows of the projection
+// Jacobian in the camera (pinhole: (sm, 0, a2) and (0, sm, a5)), p = T_imu_cam * xyz_ref = R_imu_cam * X',
+// X' = xyz_ref + tau, the reference's rows are
+//   a = [R_imu_cam alpha, p x (R_imu_cam alpha)] = blockdiag(R_imu_cam, R_imu_cam) * a',   a' = [alpha, X' x alpha]
+// so the sums over the patches are taken of the rotation-free rows a', b' and rotated once per pass (rotate_sums):
+//   H = Q H' Q^T, g = Q g', Q = blockdiag(R_imu_cam, R_imu_cam [, 1, 1]).
+// This takes R_cam_imu to be R_imu_cam^T (the two transformations of a frame are inverses of each other: the host
+// refuses a pair that is not, enqueue_align); -x/z is taken as -x * (1/z).  Same real numbers as the reference's rows,
+// last-bit differences, inside the stated tolerance of H and g.
+// to_cam0 (compiled in with MC only: every build but the 128-thread one): a camera >= 1 of a rig -- the lanes' sums mix the cameras, so its rows are turned
+// into camera 0's frame (jc[12..21)) and the pass's one rotation is camera 0's.
+struct ProjRows { double al[3], be[3]; };   // dense (use_distortion_jacobian) or sm = al[0] = be[1], al[2], be[2]
+__device__ __forceinline__ ProjRows proj_rows(const CamModel& cm, bool use_distortion_jac, const Vec3& X, double scale)
 {
-  // xyz_in_imu = T_imu_cam * xyz_ref
-  const Vec3 p = { jc[0] * X.x + jc[1] * X.y + jc[2] * X.z + jc[9], jc[3] * X.x + jc[4] * X.y + jc[5] * X.z + jc[10],
-                   jc[6] * X.x + jc[7] * X.y + jc[8] * X.z + jc[11] };
-  const double* R = jc + 12;
-  double B[6];
+  ProjRows r;
   if (!use_distortion_jac) {
-    // A = -(1/z) [1 0 -x/z; 0 1 -y/z] * |fx| * scale  (the two zeros are not multiplied out)
+    // -(1/z) [1 0 -x/z; 0 1 -y/z] * |fx| * scale  (the two zeros are never multiplied out)
+    // (1/z kept in the feature's workspace row in the place of the state value, the states on its zero and on the sign of v: measured,
+    // inside the spread of the step time -- profiles/r10_align_camera_frame_ab.txt -- and not kept)
     const double rz = 1.0 / X.z;
     const double sm = -rz * (fabs(cm.fx) * scale);
-    const double a2 = sm * (-X.x * rz), a5 = sm * (-X.y * rz);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      B[c] = sm * R[c] + a2 * R[6 + c];
-      B[3 + c] = sm * R[3 + c] + a5 * R[6 + c];
-    }
+    r.al[0] = sm; r.al[1] = 0.0; r.al[2] = sm * (-X.x * rz);
+    r.be[0] = 0.0; r.be[1] = sm; r.be[2] = sm * (-X.y * rz);
   } else {
     double A[6];
     project3_jacobian(cm, X, A);
     const double m = -scale;
 #pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        B[r * 3 + c] = (A[r * 3 + 0] * R[c] + A[r * 3 + 1] * R[3 + c] + A[r * 3 + 2] * R[6 + c]) * m;
+    for (int c = 0; c < 3; ++c) { r.al[c] = A[c] * m; r.be[c] = A[3 + c] * m; }
   }
-  // G_x = [I, -skew(p)]
-  a[0] = B[0]; a[1] = B[1]; a[2] = B[2];
-  a[3] = B[1] * (-p.z) + B[2] * p.y;
-  a[4] = B[0] * p.z + B[2] * (-p.x);
-  a[5] = B[0] * (-p.y) + B[1] * p.x;
-  b[0] = B[3]; b[1] = B[4]; b[2] = B[5];
-  b[3] = B[4] * (-p.z) + B[5] * p.y;
-  b[4] = B[3] * p.z + B[5] * (-p.x);
-  b[5] = B[3] * (-p.y) + B[4] * p.x;
+  return r;
 }
-
+// v[0..3), v[3..6) <- M v[0..3), M v[3..6)   (M row-major)
+__device__ __forceinline__ void rotate_halves(const double* M, double (&v)[6])
+{
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const double x = v[3 * h], y = v[3 * h + 1], z = v[3 * h + 2];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) v[3 * h + r] = M[3 * r] * x + M[3 * r + 1] * y + M[3 * r + 2] * z;
+  }
+}
 // One patch, pixel part: interpolated reference patch with border and its
 // central differences (a-5), interpolated current patch and residual (a-6),
 // robust weight (a-7), reduced to the weighted moments of (dx, dy, I_ref, 1)
@@ -646,14 +647,112 @@ __device__ __forceinline__ void accumulate_patch(const double (&mom)[AccLayout<D
   acc[NH + D] += mom[5];
 }
 
-// Gradient-only form of the above for the iterations that reuse the level's Hessian: accg = (g[0..D), chi2).
-template <int D>
-__device__ __forceinline__ void accumulate_patch_gradient(const double (&mom)[AccLayout<D>::NMOM], const double (&a)[6],
-                                                          const double (&b)[6], bool est_alpha, bool est_beta,
-                                                          double (&accg)[D + 1])
+// The same map for the camera-frame rows of the plain pinhole Jacobian, six parameters: a[1] = b[0] = 0, and the terms with them
+// are left out (the compiler may not do that: x * 0 is not 0 for every x).  Six parameters only: a second copy of the
+// eight-parameter map -- 45 sums, 15 moments -- costs its kernels 150 - 250 spilled registers.
+__device__ __forceinline__ void accumulate_patch_pinhole(const double (&mom)[AccLayout<6>::NMOM], const double (&a)[6], const double (&b)[6],
+                                                         double (&acc)[AccLayout<6>::NACC])
 {
+  constexpr int NH = AccLayout<6>::NH;
+  double u[6], v[6];
+  u[0] = mom[0] * a[0]; v[0] = mom[1] * a[0];
+  u[1] = mom[1] * b[1]; v[1] = mom[2] * b[1];
 #pragma unroll
-  for (int i = 0; i < 6; ++i) accg[i] -= a[i] * mom[3] + b[i] * mom[4];
+  for (int k = 2; k < 6; ++k) {
+    u[k] = mom[0] * a[k] + mom[1] * b[k];
+    v[k] = mom[1] * a[k] + mom[2] * b[k];
+  }
+  int idx = 0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+#pragma unroll
+    for (int j = i; j < 6; ++j) {
+      if (j == 0) acc[idx] += u[i] * a[j];
+      else if (j == 1) acc[idx] += v[i] * b[j];
+      else acc[idx] += u[i] * a[j] + v[i] * b[j];
+      ++idx;
+    }
+  }
+  acc[NH + 0] -= a[0] * mom[3];
+  acc[NH + 1] -= b[1] * mom[4];
+#pragma unroll
+  for (int i = 2; i < 6; ++i) acc[NH + i] -= a[i] * mom[3] + b[i] * mom[4];
+  acc[NH + 6] += mom[5];
+}
+
+// The camera-frame rows of a patch (see proj_rows)
+// (returns whether the rows are dense: false = the pinhole rows with a[1] = b[0] = 0)
+template <bool MC>
+__device__ __forceinline__ bool jac_rows_cam(const double* jc, bool to_cam0, const CamModel& cm, bool use_distortion_jac, const Vec3& X,
+                                             double scale, double (&a)[6], double (&b)[6])
+{
+  const ProjRows r = proj_rows(cm, use_distortion_jac, X, scale);
+  const Vec3 Xp = { X.x + jc[9], X.y + jc[10], X.z + jc[11] };
+  a[0] = r.al[0]; a[2] = r.al[2];
+  b[1] = r.be[1]; b[2] = r.be[2];
+  if (!use_distortion_jac) {
+    const double sm = r.al[0];
+    a[1] = 0.0; b[0] = 0.0;
+    a[3] = Xp.y * r.al[2];
+    a[4] = Xp.z * sm - Xp.x * r.al[2];
+    a[5] = -(Xp.y * sm);
+    b[3] = Xp.y * r.be[2] - Xp.z * sm;
+    b[4] = -(Xp.x * r.be[2]);
+    b[5] = Xp.x * sm;
+  } else {
+    a[1] = r.al[1]; b[0] = r.be[0];
+    a[3] = Xp.y * r.al[2] - Xp.z * r.al[1];
+    a[4] = Xp.z * r.al[0] - Xp.x * r.al[2];
+    a[5] = Xp.x * r.al[1] - Xp.y * r.al[0];
+    b[3] = Xp.y * r.be[2] - Xp.z * r.be[1];
+    b[4] = Xp.z * r.be[0] - Xp.x * r.be[2];
+    b[5] = Xp.x * r.be[1] - Xp.y * r.be[0];
+  }
+  bool dense = use_distortion_jac;
+  if constexpr (MC) {
+    if (to_cam0) { rotate_halves(jc + 12, a); rotate_halves(jc + 12, b); dense = true; }
+  }
+  return dense;
+}
+template <int D>
+__device__ __forceinline__ void accumulate_patch_rows(const double (&mom)[AccLayout<D>::NMOM], const double (&a)[6], const double (&b)[6], bool dense,
+                                                      bool est_alpha, bool est_beta, double (&acc)[AccLayout<D>::NACC])
+{
+  if constexpr (D == 6) {
+    if (dense) accumulate_patch<D>(mom, a, b, est_alpha, est_beta, acc);
+    else accumulate_patch_pinhole(mom, a, b, acc);
+  } else {
+    accumulate_patch<D>(mom, a, b, est_alpha, est_beta, acc);
+  }
+}
+
+// Gradient-only form of the above for the iterations that reuse the level's Hessian: accg = (g[0..D), chi2).
+// The rows are never formed: with s = alpha * Sxr + beta * Syr (camera frame, see jac_rows_cam) the patch's share of
+// the gradient is -[s, X' x s].
+template <int D, bool MC>
+__device__ __forceinline__ void accumulate_patch_gradient(const double (&mom)[AccLayout<D>::NMOM], const double* jc, bool to_cam0,
+                                                          const CamModel& cm, bool use_distortion_jac, const Vec3& X, double scale,
+                                                          bool est_alpha, bool est_beta, double (&accg)[D + 1])
+{
+  const ProjRows r = proj_rows(cm, use_distortion_jac, X, scale);
+  const Vec3 Xp = { X.x + jc[9], X.y + jc[10], X.z + jc[11] };
+  double s[6];
+  if (!use_distortion_jac) {
+    s[0] = r.al[0] * mom[3];
+    s[1] = r.be[1] * mom[4];
+  } else {
+    s[0] = r.al[0] * mom[3] + r.be[0] * mom[4];
+    s[1] = r.al[1] * mom[3] + r.be[1] * mom[4];
+  }
+  s[2] = r.al[2] * mom[3] + r.be[2] * mom[4];
+  s[3] = Xp.y * s[2] - Xp.z * s[1];
+  s[4] = Xp.z * s[0] - Xp.x * s[2];
+  s[5] = Xp.x * s[1] - Xp.y * s[0];
+  if constexpr (MC) {
+    if (to_cam0) rotate_halves(jc + 12, s);
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) accg[i] -= s[i];
   if constexpr (D == 8) {
     if (est_alpha) accg[6] += mom[13];
     if (est_beta) accg[7] += mom[14];
@@ -802,11 +901,11 @@ __device__ __forceinline__ double* ws_pair(const WsView& w, int pair, int64_t gi
 // visibility differs from the one recorded by the last full pass (the state value of its workspace row) -- the
 // caller then repeats the iteration with a full pass.  A full pass records the visibility.
 // jc: the camera's kJacConsts block (LDS).
-template <int P, int D, int NT, bool LDS, bool GONLY = false, bool ROB = false>
+template <int P, int D, int NT, bool LDS, bool MC, bool GONLY = false, bool ROB = false>
 __device__ __forceinline__ void accumulate_camera(
     const AlignKernelArgs& a, const WsView& ws, const CamPass& cd, const ImgView<LDS>& ref, const ImgView<LDS>& cur, int cw, int ch,
     const Rigid& Tcr, double scale, double one_plus_alpha, double beta_d, bool est_alpha, bool est_beta,
-    bool robust, bool dist_jac, float weight_scale, int tid, const double* jc,
+    bool robust, bool dist_jac, float weight_scale, int tid, const double* jc, bool to_cam0,
     double (&acc)[GONLY ? D + 1 : AccLayout<D>::NACC], int& nvis, int& changed, int stride = NT)
 {
   SVOH_PASS_STAMP_BEGIN();
@@ -868,10 +967,12 @@ __device__ __forceinline__ void accumulate_camera(
         if (!GONLY || k == 3 || k == 4 || k == 5 || k == 13 || k == 14) asm volatile("" : "+v"(mom[k]));
     }
     SVOH_PASS_STAMP(3);
-    double ja[6], jb[6];
-    jac_rows(jc, cm, dist_jac, X, scale, ja, jb);
-    if constexpr (GONLY) accumulate_patch_gradient<D>(mom, ja, jb, est_alpha, est_beta, acc);
-    else accumulate_patch<D>(mom, ja, jb, est_alpha, est_beta, acc);
+    if constexpr (GONLY) accumulate_patch_gradient<D, MC>(mom, jc, to_cam0, cm, dist_jac, X, scale, est_alpha, est_beta, acc);
+    else {
+      double ja[6], jb[6];
+      const bool dense = jac_rows_cam<MC>(jc, to_cam0, cm, dist_jac, X, scale, ja, jb);
+      accumulate_patch_rows<D>(mom, ja, jb, dense, est_alpha, est_beta, acc);
+    }
 #ifdef SVOH_PHASE_STAMPS
     asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]));
 #endif
@@ -884,11 +985,11 @@ __device__ __forceinline__ void accumulate_camera(
 // bytes: one request), projection and visibility, the Jacobian rows -- is computed by every lane of the group alike:
 // identical values, no exchange, and no divergence inside a group.  The patch is counted and its visibility recorded
 // by the group's lane 0.
-template <int P, int LPP, int D, int NT, bool LDS, bool GONLY = false, bool ROB = false>
+template <int P, int LPP, int D, int NT, bool LDS, bool MC, bool GONLY = false, bool ROB = false>
 __device__ __forceinline__ void accumulate_camera_rows(
     const AlignKernelArgs& a, const WsView& ws, const CamPass& cd, const ImgView<LDS>& ref, const ImgView<LDS>& cur, int cw, int ch,
     const Rigid& Tcr, double scale, double one_plus_alpha, double beta_d, bool est_alpha, bool est_beta,
-    bool robust, bool dist_jac, float weight_scale, int tid, const double* jc,
+    bool robust, bool dist_jac, float weight_scale, int tid, const double* jc, bool to_cam0,
     double (&acc)[GONLY ? D + 1 : AccLayout<D>::NACC], int& nvis, int& changed, int stride = NT)
 {
   static_assert(LPP == 2 || LPP == 4 || LPP == 8, "a group is 2, 4 or 8 consecutive lanes");
@@ -946,10 +1047,12 @@ __device__ __forceinline__ void accumulate_camera_rows(
     for (int k = 0; k < AccLayout<D>::NMOM; ++k)
       if (!GONLY || k == 3 || k == 4 || k == 5 || k == 13 || k == 14) asm volatile("" : "+v"(mom[k]));
     SVOH_PASS_STAMP(3);
-    double ja[6], jb[6];
-    jac_rows(jc, cm, dist_jac, X, scale, ja, jb);
-    if constexpr (GONLY) accumulate_patch_gradient<D>(mom, ja, jb, est_alpha, est_beta, acc);
-    else accumulate_patch<D>(mom, ja, jb, est_alpha, est_beta, acc);
+    if constexpr (GONLY) accumulate_patch_gradient<D, MC>(mom, jc, to_cam0, cm, dist_jac, X, scale, est_alpha, est_beta, acc);
+    else {
+      double ja[6], jb[6];
+      const bool dense = jac_rows_cam<MC>(jc, to_cam0, cm, dist_jac, X, scale, ja, jb);
+      accumulate_patch_rows<D>(mom, ja, jb, dense, est_alpha, est_beta, acc);
+    }
 #ifdef SVOH_PHASE_STAMPS
     asm volatile("" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]));
 #endif
@@ -966,11 +1069,11 @@ __device__ __forceinline__ void accumulate_camera_rows(
 // stage: this wave's 2 x 3 x 64 x 16 B staging area.  Control flow is wave-uniform (every lane runs every pass).
 constexpr int kStageDoubles = 2 * kWsPairs * 128;
 // LDS / CLDS: where the reference and the current image of the level are (they differ on a half-resident level)
-template <int P, int D, int NT, bool LDS, bool GONLY = false, bool ROB = false, bool CLDS = LDS>
+template <int P, int D, int NT, bool LDS, bool MC, bool GONLY = false, bool ROB = false, bool CLDS = LDS>
 __device__ __forceinline__ void accumulate_camera_staged(
     const AlignKernelArgs& a, const CamPass& cd, const ImgView<LDS>& ref, const ImgView<CLDS>& cur, int cw, int ch,
     const Rigid& Tcr, double scale, double one_plus_alpha, double beta_d, bool est_alpha, bool est_beta,
-    bool robust, bool dist_jac, float weight_scale, int tid, double* stage, const double* jc,
+    bool robust, bool dist_jac, float weight_scale, int tid, double* stage, const double* jc, bool to_cam0,
     double (&acc)[GONLY ? D + 1 : AccLayout<D>::NACC], int& nvis, int& changed, int stride = NT)
 {
   typedef const __attribute__((address_space(1))) void* gptr;
@@ -1046,13 +1149,66 @@ __device__ __forceinline__ void accumulate_camera_staged(
       const double2 xy2 = *reinterpret_cast<const double2*>(buf + 0 * 128 + lane * 2);
       const double z2 = buf[1 * 128 + lane * 2];
       const Vec3 X = { xy2.x, xy2.y, z2 };
-      double ja[6], jb[6];
-      jac_rows(jc, cm, dist_jac, X, scale, ja, jb);
-      if constexpr (GONLY) accumulate_patch_gradient<D>(mom, ja, jb, est_alpha, est_beta, acc);
-      else accumulate_patch<D>(mom, ja, jb, est_alpha, est_beta, acc);
+      if constexpr (GONLY) accumulate_patch_gradient<D, MC>(mom, jc, to_cam0, cm, dist_jac, X, scale, est_alpha, est_beta, acc);
+      else {
+        double ja[6], jb[6];
+        const bool dense = jac_rows_cam<MC>(jc, to_cam0, cm, dist_jac, X, scale, ja, jb);
+        accumulate_patch_rows<D>(mom, ja, jb, dense, est_alpha, est_beta, acc);
+      }
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0) before the next pass may request this buffer again
   }
+}
+
+// The pass's one rotation.  The waves' sums are those of the camera-frame rows (jac_rows_cam): H', g'.  The threads that add
+// them across the waves write g_sum = Q H' Q^T, Q g' with Q = blockdiag(R, R [, 1, 1]) (R = camera 0's R_imu_cam), one
+// thread per entry: it adds the (up to nine) entries its own needs over the waves, each in the order of the plain sum, and
+// applies R -- nine products.  No barrier more than the plain sum had (the extra LDS reads are independent of each other;
+// a second barrier and a second buffer would cost a 128-thread workgroup more than 16 reads), and whoever reads g_sum --
+// the step, the evaluation's output, the raw sums of a share, the cluster's exchange -- sees the IMU-frame sums.
+// GONLY: red[w] holds (g', chi2) and g_sum[0 .. NH) keeps the level's rotated Hessian.
+// Out of line, like the step: inlined, its index arithmetic shares the patch loops' register allocation and they pay for it with
+// spills (8x8 kernel: 528 B of scratch against the 480 B it had; out of line 464 B).  red (the waves' sums, NW rows of NACC) and
+// R are handed over as LDS addresses, so that the reads stay ds_read.
+typedef const __attribute__((address_space(3))) double* LdsConstDoubles;
+template <int D, int NW, int NACC, bool GONLY>
+__device__ __attribute__((noinline)) void rotate_sums(LdsConstDoubles red, LdsConstDoubles R, int tid)
+{
+  constexpr int NH = AccLayout<D>::NH;
+  auto sum = [&](int k) {
+    double v = 0.0;
+    for (int w = 0; w < NW; ++w) v += red[w * NACC + k];
+    return v;
+  };
+  auto rot3 = [&](int r, int first, int step) {   // row r of R times three sums
+    return R[3 * r] * sum(first) + R[3 * r + 1] * sum(first + step) + R[3 * r + 2] * sum(first + 2 * step);
+  };
+  if (tid >= (GONLY ? D + 1 : NACC)) return;
+  const int gi = GONLY ? tid : tid - NH;   // index into (g, chi2); negative: an entry of H
+  double v;
+  if (gi >= 0) {
+    const int b = gi >= 3 ? 3 : 0;
+    v = gi < 6 ? rot3(gi - b, (GONLY ? 0 : NH) + b, 1) : sum(tid);
+  } else {
+    int i = 0, j = tid;   // the entry's row and column (upper triangle, row by row)
+    while (j >= D - i) { j -= D - i; ++i; }
+    j += i;
+    auto packed = [](int k, int l) { if (k > l) { const int t = k; k = l; l = t; } return k * D - k * (k - 1) / 2 + (l - k); };
+    if (i >= 6) v = sum(tid);
+    else {
+      const int bi = i >= 3 ? 3 : 0, r = i - bi;
+      if (j >= 6) v = R[3 * r] * sum(packed(bi, j)) + R[3 * r + 1] * sum(packed(bi + 1, j)) + R[3 * r + 2] * sum(packed(bi + 2, j));
+      else {
+        const int bj = j >= 3 ? 3 : 0, c = j - bj;
+        v = 0.0;
+        for (int k = 0; k < 3; ++k) {
+          const double hk = sum(packed(bi + k, bj)) * R[3 * c] + sum(packed(bi + k, bj + 1)) * R[3 * c + 1] + sum(packed(bi + k, bj + 2)) * R[3 * c + 2];
+          v += R[3 * r + k] * hk;
+        }
+      }
+    }
+  }
+  g_sum[GONLY ? NH + tid : tid] = v;
 }
 
 // Cluster mode: replace vals[0 .. n) (LDS) by their sums over the workgroups of the cluster, added in share order
@@ -1443,6 +1599,11 @@ void sparse_align_kernel(const AlignKernelArgs a)
   static_assert(LPP == 1 || (!CLUSTER && NT == 512 && LPP <= P), "rows geometry: 512 threads, no cluster mode");
   static_assert(NT == 128 || NT == 256 || NT == 512, "workgroups of 128, 256 or 512 threads");
   static_assert(NT != 128 || (!CLUSTER && !LAT && !RIG && LPP == 1), "128 threads: the batch geometry only");
+  // The arm that turns the rows of a rig's cameras >= 1 into camera 0's frame (jac_rows_cam): a wave-uniform branch in the patch loop of
+  // every build but the 128-thread one, which the host gives single-camera launches only (decide_geometry).  The 256-thread batch build
+  // serves launches with and without rigs with ONE kernel: a problem's result must be the same bits whatever else shares its launch
+  // (AlignGeometry), and two instantiations of the same source do not round alike.
+  constexpr bool kMultiCam = NT != 128;
   constexpr bool ROWS = LPP > 1;
   constexpr int D = ILLUM ? 8 : 6;
   constexpr int NACC = AccLayout<D>::NACC;
@@ -1463,7 +1624,7 @@ void sparse_align_kernel(const AlignKernelArgs a)
   // choice: no difference, profiles/r09_align_wg128_ab.txt).
   extern __shared__ __align__(16) unsigned char lds_img[];
   __shared__ __align__(16) double s_stage[STAGED ? NW * kStageDoubles : 2];
-  __shared__ double s_jc[SVOH_MAX_CAMS][kJacConsts];   // per-camera constants of jac_rows
+  __shared__ double s_jc[SVOH_MAX_CAMS][kJacConsts];   // per-camera constants of the camera-frame rows and of the pass's rotation (kJacConsts)
   __shared__ int s_lvl_off[SVOH_MAX_LEVELS];           // where the level's images start in lds_img; -1: not resident
   __shared__ double s_red[NW][NACC];
   static_assert(NACC <= 45, "g_sum is sized for the 8-parameter case");
@@ -1580,10 +1741,14 @@ void sparse_align_kernel(const AlignKernelArgs a)
     for (int c = 0; c < n_cams; ++c) {
       g_state.cam_cur_T_cam_imu[c] = load_rigid(cams[c].cur_T_cam_imu);
       g_state.cam_ref_T_imu_cam[c] = load_rigid(cams[c].ref_T_imu_cam);
-      to_matrix(g_state.cam_ref_T_imu_cam[c].q, &s_jc[c][0]);
-      s_jc[c][9] = g_state.cam_ref_T_imu_cam[c].t.x; s_jc[c][10] = g_state.cam_ref_T_imu_cam[c].t.y;
-      s_jc[c][11] = g_state.cam_ref_T_imu_cam[c].t.z;
-      to_matrix(load_rigid(cams[c].ref_T_cam_imu).q, &s_jc[c][12]);
+      // the constants of jac_rows_cam: R_imu_cam, tau = R_imu_cam^T t_imu_cam and, behind camera 0, what takes the camera's rows to camera 0's frame
+      double* jc = s_jc[c];
+      to_matrix(g_state.cam_ref_T_imu_cam[c].q, jc);
+      const Vec3 t = g_state.cam_ref_T_imu_cam[c].t;
+      for (int k = 0; k < 3; ++k) jc[9 + k] = jc[k] * t.x + jc[3 + k] * t.y + jc[6 + k] * t.z;
+      if (kMultiCam && c > 0)
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) jc[12 + 3 * i + j] = s_jc[0][i] * jc[j] + s_jc[0][3 + i] * jc[3 + j] + s_jc[0][6 + i] * jc[6 + j];
     }
 #ifdef SVOH_PHASE_STAMPS
     for (int k = 0; k < 4; ++k) g_state.dbg[k] = 0;
@@ -1808,9 +1973,9 @@ void sparse_align_kernel(const AlignKernelArgs a)
                 ImgView<false> cur;
                 ref.p = (const __attribute__((address_space(3))) uint8_t*)lds_img; ref.pitch = rim.w;
                 cur.p = cim.data; cur.pitch = cim.pitch;
-                accumulate_camera_staged<P, D, NT, true, G, ROBUST, false>(a, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
+                accumulate_camera_staged<P, D, NT, true, kMultiCam, G, ROBUST, false>(a, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
                                                                                    est_alpha, est_beta, robust, dist_jac, weight_scale, (int)cam_t,
-                                                                                   s_stage + wave * kStageDoubles, s_jc[c], acc_ref, nvis, changed, (int)cam_stride);
+                                                                                   s_stage + wave * kStageDoubles, s_jc[c], c > 0, acc_ref, nvis, changed, (int)cam_stride);
               }
             } else if (in_lds) {
               ImgView<true> ref, cur;
@@ -1820,18 +1985,18 @@ void sparse_align_kernel(const AlignKernelArgs a)
               off += ((cim.w * cim.h + 15) & ~15);
               if constexpr (ROWS) {
                 if (!RIG || cam_t < cam_stride)
-                  accumulate_camera_rows<P, (ROWS ? LPP : 2), D, NT, true, G, ROBUST>(a, ws, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
-                                                                            est_alpha, est_beta, robust, dist_jac, weight_scale, (int)cam_t, s_jc[c],
+                  accumulate_camera_rows<P, (ROWS ? LPP : 2), D, NT, true, kMultiCam, G, ROBUST>(a, ws, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
+                                                                            est_alpha, est_beta, robust, dist_jac, weight_scale, (int)cam_t, s_jc[c], c > 0,
                                                                             acc_ref, nvis, changed, (int)cam_stride);
               } else if constexpr (STAGED) {
                 if (!RIG || cam_t < cam_stride)
-                  accumulate_camera_staged<P, D, NT, true, G, ROBUST>(a, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
+                  accumulate_camera_staged<P, D, NT, true, kMultiCam, G, ROBUST>(a, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
                                                             est_alpha, est_beta, robust, dist_jac, weight_scale, (int)cam_t,
-                                                            s_stage + wave * kStageDoubles, s_jc[c], acc_ref, nvis, changed, (int)cam_stride);
+                                                            s_stage + wave * kStageDoubles, s_jc[c], c > 0, acc_ref, nvis, changed, (int)cam_stride);
               }
               else if (!RIG || cam_t < cam_stride)   // (unsigned: the lanes of the cameras in front are "negative")
-                accumulate_camera<P, D, NT, true, G, ROBUST>(a, ws, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
-                                                     est_alpha, est_beta, robust, dist_jac, weight_scale, (int)cam_t, s_jc[c], acc_ref,
+                accumulate_camera<P, D, NT, true, kMultiCam, G, ROBUST>(a, ws, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
+                                                     est_alpha, est_beta, robust, dist_jac, weight_scale, (int)cam_t, s_jc[c], c > 0, acc_ref,
                                                      nvis, changed, (int)cam_stride);
             } else {
               ImgView<false> ref, cur;
@@ -1839,18 +2004,18 @@ void sparse_align_kernel(const AlignKernelArgs a)
               cur.p = cim.data; cur.pitch = cim.pitch;
               if constexpr (ROWS) {
                 if (!RIG || cam_t < cam_stride)
-                  accumulate_camera_rows<P, (ROWS ? LPP : 2), D, NT, false, G, ROBUST>(a, ws, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
-                                                                             est_alpha, est_beta, robust, dist_jac, weight_scale, (int)cam_t, s_jc[c],
+                  accumulate_camera_rows<P, (ROWS ? LPP : 2), D, NT, false, kMultiCam, G, ROBUST>(a, ws, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
+                                                                             est_alpha, est_beta, robust, dist_jac, weight_scale, (int)cam_t, s_jc[c], c > 0,
                                                                              acc_ref, nvis, changed, (int)cam_stride);
               } else if constexpr (STAGED) {
                 if (!RIG || cam_t < cam_stride)
-                  accumulate_camera_staged<P, D, NT, false, G, ROBUST>(a, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
+                  accumulate_camera_staged<P, D, NT, false, kMultiCam, G, ROBUST>(a, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
                                                              est_alpha, est_beta, robust, dist_jac, weight_scale, (int)cam_t,
-                                                             s_stage + wave * kStageDoubles, s_jc[c], acc_ref, nvis, changed, (int)cam_stride);
+                                                             s_stage + wave * kStageDoubles, s_jc[c], c > 0, acc_ref, nvis, changed, (int)cam_stride);
               }
               else if (!RIG || cam_t < cam_stride)   // (unsigned: the lanes of the cameras in front are "negative")
-                accumulate_camera<P, D, NT, false, G, ROBUST>(a, ws, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
-                                                      est_alpha, est_beta, robust, dist_jac, weight_scale, (int)cam_t, s_jc[c], acc_ref,
+                accumulate_camera<P, D, NT, false, kMultiCam, G, ROBUST>(a, ws, cd, ref, cur, cim.w, cim.h, Tcr, scale, one_plus_alpha, beta_d,
+                                                      est_alpha, est_beta, robust, dist_jac, weight_scale, (int)cam_t, s_jc[c], c > 0, acc_ref,
                                                       nvis, changed, (int)cam_stride);
             }
           }
@@ -1881,11 +2046,8 @@ void sparse_align_kernel(const AlignKernelArgs a)
           nvis = wave_sum_i32_dpp(nvis);
           if (lane == 0) atomicAdd(&g_nvis, nvis);
           __syncthreads();
-          if (tid < D + 1) {   // gradient and chi2 only: g_sum[0 .. NH) still holds the level's Hessian
-            double v = 0.0;
-            for (int w = 0; w < NW; ++w) v += s_red[w][tid];
-            g_sum[AccLayout<D>::NH + tid] = v;
-          }
+          // gradient and chi2 only: g_sum[0 .. NH) still holds the level's (rotated) Hessian
+          rotate_sums<D, NW, NACC, true>((LdsConstDoubles)&s_red[0][0], (LdsConstDoubles)s_jc[0], tid);
           __syncthreads();
           if (cluster) {   // gradient, chi2, visible count and the visibility vote of all shares
             if (tid < D + 1) s_x[tid] = g_sum[AccLayout<D>::NH + tid];
@@ -1920,11 +2082,7 @@ void sparse_align_kernel(const AlignKernelArgs a)
           nvis = wave_sum_i32_dpp(nvis);
           if (lane == 0) atomicAdd(&g_nvis, nvis);
           __syncthreads();
-          if (tid < NACC) {
-            double v = 0.0;
-            for (int w = 0; w < NW; ++w) v += s_red[w][tid];
-            g_sum[tid] = v;
-          }
+          rotate_sums<D, NW, NACC, false>((LdsConstDoubles)&s_red[0][0], (LdsConstDoubles)s_jc[0], tid);
           __syncthreads();
           if (cluster) {
             if (tid < NACC) s_x[tid] = g_sum[tid];
@@ -2193,13 +2351,14 @@ static int decide_cluster(const svoh_ctx* ctx, int n_problems, const svoh_align_
 }
 
 // what pass 1 of enqueue_align learns about the problems of a launch, as far as the geometry depends on it
-struct LaunchShape { int max_feat_per_problem = 0; bool have_rig = false, rig_wants_512 = false; };
+struct LaunchShape { int max_feat_per_problem = 0; bool have_rig = false, rig_wants_512 = false, multi_cam = false; };
 static void add_to_shape(const svoh_align_problem& pb, int S, LaunchShape* z)
 {
   int nf = 0;
   for (int c = 0; c < pb.n_cams; ++c) nf += pb.cams[c].n_features > 0 ? pb.cams[c].n_features : 0;
   const int per_share = S > 1 ? nf / S + pb.n_cams : nf;
   if (per_share > z->max_feat_per_problem) z->max_feat_per_problem = per_share;
+  if (pb.n_cams >= 2) z->multi_cam = true;   // (shares of a split or clustered rig as well)
   if (S == 1 && pb.n_cams >= 2) {
     z->have_rig = true;
     int lanes = 0;
@@ -2245,7 +2404,7 @@ static AlignGeometry decide_geometry(const svoh_ctx* ctx, const svoh_align_optio
   // problem's latency-bound phases (base phase, level set-up, reductions, the step) weigh half as much against its passes, so the
   // SIMDs stand idle less.  Single-camera problems with 4x4 patches (8x8 patches lose 3 % there), kAlign128MinRounds rounds
   // of four per compute unit or more.  SVOH_ALIGN_THREADS=128 asks for it at any size, =256 keeps the two-workgroup build.
-  const bool can_128 = !cluster && !z.have_rig;
+  const bool can_128 = !cluster && !z.have_rig && !z.multi_cam;   // (its patch loop has no arm for a second camera)
   if (can_128 && nt == 256 && opt->patch_size == 4 && n_desc >= kAlign128MinRounds * 4 * ctx->num_cus) nt = 128;
   nt = SvohKnobs::or_default(ctx->knobs.align_threads, nt);
   if (cluster) nt = 256;   // one workgroup per CU at most: all of them are resident together
@@ -2459,13 +2618,28 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
       }
       dc.cam = cam.cam;
       {
-        // The Jacobian rows take p_in_cam = T_cam_imu * (T_imu_cam * xyz_ref) to be xyz_ref itself (jac_rows): the two
-        // extrinsic transformations of the reference frame must be inverses of each other, as they are in a
-        // reference Frame (frame.h:342-357 builds both from one T_cam_imu).  A pair that is not would silently get
-        // a different Jacobian than the reference computes: refused instead.
-        const Rigid I = mul(load_rigid(cam.ref_T_cam_imu), load_rigid(cam.ref_T_imu_cam));
-        const double dev = fmax(fmax(fabs(fabs(I.q.w) - 1.0), fmax(fabs(I.q.x), fmax(fabs(I.q.y), fabs(I.q.z)))),
-                                fmax(fabs(I.t.x), fmax(fabs(I.t.y), fabs(I.t.z))));
+        // The Jacobian rows are formed in the camera frame from T_imu_cam alone and rotated once per pass (jac_rows_cam,
+        // rotate_sums): R_cam_imu is taken to be R_imu_cam^T and p_in_cam = T_cam_imu * (T_imu_cam * xyz_ref) to be
+        // xyz_ref itself.  The two extrinsic transformations of the reference frame must therefore be inverses of each
+        // other, as they are in a reference Frame (frame.h:342-357 builds both from one T_cam_imu).  A pair that is not
+        // would silently get a different Jacobian than the reference computes: refused instead.  Measured as the
+        // largest entry of R_imu_cam R_cam_imu - I and of t_imu_cam + R_imu_cam t_cam_imu, that one relative to 1 + |t|.
+        const Rigid Tic = load_rigid(cam.ref_T_imu_cam), Tci = load_rigid(cam.ref_T_cam_imu);
+        double Ric[9], Rci[9];
+        to_matrix(Tic.q, Ric);
+        to_matrix(Tci.q, Rci);
+        double dev = 0.0;
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) {
+            const double e = Ric[3 * i] * Rci[j] + Ric[3 * i + 1] * Rci[3 + j] + Ric[3 * i + 2] * Rci[6 + j] - (i == j ? 1.0 : 0.0);
+            dev = fabs(e) > dev || e != e ? fabs(e) : dev;
+          }
+        const double tic[3] = { Tic.t.x, Tic.t.y, Tic.t.z };
+        const double tn = 1.0 + sqrt(tic[0] * tic[0] + tic[1] * tic[1] + tic[2] * tic[2]);
+        for (int i = 0; i < 3; ++i) {
+          const double e = (tic[i] + Ric[3 * i] * Tci.t.x + Ric[3 * i + 1] * Tci.t.y + Ric[3 * i + 2] * Tci.t.z) / tn;
+          dev = fabs(e) > dev || e != e ? fabs(e) : dev;
+        }
         if (!(dev <= 1e-9))
           return set_error(ctx, SVOH_ERR_INVALID_ARGUMENT,
                            "problem %d camera %d: ref_T_cam_imu is not the inverse of ref_T_imu_cam (deviation %.3g)", p, c, dev);
@@ -2537,6 +2711,7 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   // SVOH_ALIGN_OVERLAP=0: one lane.  On by default at every size of the batch geometry: 512 ... 4096 frame pairs per step all gain
   // (0.52 against 0.71 ms per step, 0.96 against 1.17, 2.03 against 2.21, 3.42 against 3.74: profiles/r08_align_overlap_ab.txt).
   const AlignGeometry geo = forced ? *forced : decide_geometry(ctx, opt, n_desc, cluster ? S : 0, shape);
+  SVOH_REQUIRE(ctx, !(geo.nt == 128 && shape.multi_cam), "the 128-thread geometry takes single-camera problems only");
   const int overlap_knob = ctx->knobs.align_overlap;
   const bool lane_kind = n_desc >= ctx->num_cus && (geo.nt == 256 || geo.nt == 128) && !geo.latency && !cluster && !split && !forced && eval_level < 0 && n_pos_jobs == 0 &&
                          (overlap_knob == kKnobUnset || overlap_knob != 0);
