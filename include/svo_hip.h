@@ -400,6 +400,36 @@ int svoh_sparse_align_evaluate(svoh_ctx* ctx, const svoh_align_options* options,
                                int32_t* n_meas, uint8_t* visibility,
                                int32_t* n_selected);
 
+/* ---- sparse image alignment on EQUIDISTANT / ATAN (fisheye) cameras ------ */
+
+/* svoh_sparse_align_batch and svoh_sparse_align_evaluate for problems whose cameras may be EQUIDISTANT or ATAN (every entry
+ * above refuses those).  Blocking; structures and result semantics are those of svoh_sparse_align_batch / _evaluate.
+ * If NO camera of any problem is wide the call IS svoh_sparse_align_batch / _evaluate (same kernels, same bits).  Otherwise the
+ * whole launch runs sparse_align_wide_kernel<P, ILLUM, ROBUST>, also for the NONE / RADTAN cameras beside the wide ones: ONE
+ * geometry (512 threads, a lane per patch, one workgroup per problem, a rig's cameras one after the other; no cluster mode, no
+ * lanes per patch, no latency build, no launch lanes), so a problem's result bits do not depend on what else is in its launch.
+ * Arithmetic (sparse_img_align.cpp:262-317, 405-498): every projection is a pinhole projection (kPinhole) whatever its distortion;
+ * without use_distortion_jacobian the Jacobian rows are jacobian_xyz2uv_imu times |fx|, with it minus the model's own project3
+ * Jacobian; a point with z < 0 is invisible.
+ * Refused, with nothing staged and `results` (the evaluation's outputs) untouched:
+ *   ATAN with use_distortion_jacobian (the reference has no Jacobian for it)               SVOH_ERR_UNSUPPORTED
+ *   ATAN whose s = d[0] is zero or not finite                                              SVOH_ERR_INVALID_ARGUMENT
+ *   a camera whose mem_space is not SVOH_MEM_HOST, or pos_seed_unit != NULL                SVOH_ERR_UNSUPPORTED
+ *   a call while results of earlier _enqueue calls are unfetched, or inside a deferred
+ *   matcher section (svoh_matcher_begin_deferred)                                          SVOH_ERR_INVALID_ARGUMENT
+ *                                                                                          (the queued results stay fetchable)
+ * Bookkeeping of a launch of the twin: with kernel timing on it feeds svoh_sparse_align_last_kernel_ms / _kernel_ms_history; it
+ * does NOT update svoh_sparse_align_last_launch_info, _last_launch_lds or _last_launch_lane (they go on describing the last launch
+ * of sparse_align_kernel). */
+int svoh_sparse_align_wide_batch(svoh_ctx* ctx, const svoh_align_options* options,
+                                 int n_problems, const svoh_align_problem* problems,
+                                 svoh_align_result* results);
+int svoh_sparse_align_wide_evaluate(svoh_ctx* ctx, const svoh_align_options* options,
+                                    const svoh_align_problem* problem, int level,
+                                    double* H64, double* g8, double* chi2,
+                                    int32_t* n_meas, uint8_t* visibility,
+                                    int32_t* n_selected);
+
 /* ---- patch-split Gauss-Newton (second row) -------------- */
 
 /* One alignment problem whose patches are split over several GPUs (or several

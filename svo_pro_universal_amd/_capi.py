@@ -371,6 +371,8 @@ EXPORTS = [
     "svoh_translation_ransac_batch",
     # ... and the essential-matrix estimator (csrc/essential.hip; the FivePoint initialiser)
     "svoh_essential_ransac_batch",
+    # sparse image alignment on EQUIDISTANT / ATAN cameras (sparse_align_wide_kernel)
+    "svoh_sparse_align_wide_batch", "svoh_sparse_align_wide_evaluate",
 ]
 
 
@@ -461,6 +463,8 @@ def load(path=None):
     lib.svoh_sparse_align_evaluate.argtypes = [C.c_void_p, P(svoh_align_options), P(svoh_align_problem),
                                                C.c_int, C.c_void_p, C.c_void_p, P(C.c_double),
                                                P(C.c_int32), C.c_void_p, P(C.c_int32)]
+    lib.svoh_sparse_align_wide_batch.argtypes = lib.svoh_sparse_align_batch.argtypes
+    lib.svoh_sparse_align_wide_evaluate.argtypes = lib.svoh_sparse_align_evaluate.argtypes
     lib.svoh_sparse_align_last_kernel_ms.argtypes = [C.c_void_p, P(C.c_float)]
     lib.svoh_sparse_align_kernel_ms_history.argtypes = [C.c_void_p, C.c_int, P(C.c_float), P(C.c_int)]
     lib.svoh_sparse_align_last_launch_info.argtypes = [C.c_void_p, P(C.c_int32), P(C.c_int32), P(C.c_int32)]

@@ -267,6 +267,26 @@ class Context(object):
                                                         vis.ctypes.data, C.byref(nsel)))
         return H.reshape(8, 8).T.copy(), g, chi2.value, nm.value, vis[:nsel.value].copy()
 
+    # ---- ... on EQUIDISTANT / ATAN cameras (sparse_align_wide_kernel; all-narrow problems go to the entries above) ----
+    def sparse_align_wide(self, opt, problems):
+        """svoh_sparse_align_wide_batch: sparse_align for problems whose cameras may be equidistant or atan.  Blocking."""
+        n = len(problems)
+        res = (capi.svoh_align_result * n)()
+        self._check(self.lib.svoh_sparse_align_wide_batch(self.h, C.byref(opt), n, problems, res))
+        return res
+
+    def sparse_align_wide_evaluate(self, opt, problem, level):
+        """svoh_sparse_align_wide_evaluate: (H 8x8, g, chi2, n_meas, visibility) as sparse_align_evaluate."""
+        H = np.zeros(64)
+        g = np.zeros(8)
+        chi2, nm, nsel = C.c_double(), C.c_int32(), C.c_int32()
+        ntot = sum(problem.cams[i].n_features for i in range(problem.n_cams))
+        vis = np.zeros(max(1, ntot), np.uint8)
+        self._check(self.lib.svoh_sparse_align_wide_evaluate(self.h, C.byref(opt), C.byref(problem), level,
+                                                             H.ctypes.data, g.ctypes.data, C.byref(chi2), C.byref(nm),
+                                                             vis.ctypes.data, C.byref(nsel)))
+        return H.reshape(8, 8).T.copy(), g, chi2.value, nm.value, vis[:nsel.value].copy()
+
     # ---- patch-split Gauss-Newton (SURVEY.md 8(e)); the loop itself is split_align.gauss_newton_split ----
     def split_init(self, problem, d_state):
         self._check(self.lib.svoh_sparse_align_split_init(self.h, C.byref(problem), C.c_void_p(d_state)))

@@ -110,12 +110,25 @@ size_t SparseImgAlignHip::finishRun(const svoh_align_result& result, const Frame
   return static_cast<size_t>(last_.n_fts_to_track);
 }
 
+// a camera of the bundle is EQUIDISTANT or ATAN: the bundle aligns through svoh_sparse_align_wide_batch, which is blocking
+static bool has_wide_camera(const svoh_align_problem& pb)
+{
+  for (int c = 0; c < pb.n_cams; ++c)
+    if (!svoh::camera_is_narrow(pb.cams[c].cam)) return true;
+  return false;
+}
+
 size_t SparseImgAlignHip::run(const FrameBundle::Ptr& ref_frames, const FrameBundle::Ptr& cur_frames)
 {
   svoh_align_options opt;
   svoh_align_problem pb;
   const Transformation T_iref_world = buildProblem(ref_frames, cur_frames, 0, 1, opt, pb);
   svoh_align_result res{};
+  if (has_wide_camera(pb)) {
+    const int rc = svoh_sparse_align_wide_batch(ctx_, &opt, 1, &pb, &res);
+    if (rc != SVOH_OK) throw std::runtime_error(std::string("svoh_sparse_align_wide_batch: ") + svoh_last_error_string(ctx_));
+    return finishRun(res, cur_frames, T_iref_world);
+  }
   const int rc = svoh_sparse_align_batch(ctx_, &opt, 1, &pb, &res);
   if (rc != SVOH_OK) throw std::runtime_error(std::string("svoh_sparse_align_batch: ") + svoh_last_error_string(ctx_));
   return finishRun(res, cur_frames, T_iref_world);
@@ -126,6 +139,9 @@ size_t SparseImgAlignHip::run(const FrameBundle::Ptr& ref_frames, const FrameBun
   svoh_align_options opt;
   svoh_align_problem pb;
   const Transformation T_iref_world = buildProblem(ref_frames, cur_frames, 0, 1, opt, pb);
+  if (has_wide_camera(pb))
+    throw std::runtime_error("SparseImgAlignHip::run(ref, cur, after_enqueue): a bundle with an EQUIDISTANT or ATAN camera aligns through the "
+                             "blocking overload run(ref_frames, cur_frames) only");
   last_run_repeated_ = false;
   int rc = svoh_sparse_align_enqueue(ctx_, &opt, 1, &pb);
   if (rc != SVOH_OK) throw std::runtime_error(std::string("svoh_sparse_align_enqueue: ") + svoh_last_error_string(ctx_));
@@ -147,6 +163,9 @@ size_t SparseImgAlignHip::runSplit(const FrameBundle::Ptr& ref_frames, const Fra
   svoh_align_options opt;
   svoh_align_problem pb;
   const Transformation T_iref_world = buildProblem(ref_frames, cur_frames, rank, world, opt, pb);
+  if (has_wide_camera(pb))
+    throw std::runtime_error("SparseImgAlignHip::runSplit: a bundle with an EQUIDISTANT or ATAN camera aligns through the blocking overload "
+                             "run(ref_frames, cur_frames) only");
   auto check = [this](int rc, const char* what) {
     if (rc != SVOH_OK) throw std::runtime_error(std::string(what) + ": " + svoh_last_error_string(ctx_));
   };

@@ -187,6 +187,8 @@ class SparseImgAlignHip {
   // SparseImgAlign::run: optimises the pose of cur_frames (writes T_f_w_ of every
   // frame of the bundle) and returns the number of features tracked; 0 = none.
   // Throws std::runtime_error on an ABI error (the reference CHECK-aborts).
+  // A bundle with an EQUIDISTANT or ATAN camera goes through svoh_sparse_align_wide_batch (THIS overload only: the
+  // after_enqueue overload and runSplit throw for such a bundle, the wide entry is blocking).
   size_t run(const FrameBundle::Ptr& ref_frames, const FrameBundle::Ptr& cur_frames);
   // The same with a hook between the launch and the wait for it: after_enqueue(T_iref_world) runs while the
   // alignment kernel does, and device work it queues on the context (ReprojectorHip::enqueueCandidateProjection)
