@@ -853,7 +853,7 @@ void StereoTriangulationHip::finish(const FramePtr& frame0, const FramePtr& fram
       new_point->id_ = next_point_id_++;
       f0.landmark_vec_[i_ref] = new_point;
       f0.track_id_vec_[i_ref] = new_point->id();
-      new_point->obs_.push_back(Point::Obs{ frame0, i_ref });
+      new_point->addObservation(frame0, i_ref);
       const size_t i_cur = f1.num_features_;
       f1.type_vec_[i_cur] = f0.type_vec_[i_ref];
       f1.level_vec_[i_cur] = f0.level_vec_[i_ref];
@@ -867,7 +867,7 @@ void StereoTriangulationHip::finish(const FramePtr& frame0, const FramePtr& fram
       f1.grad_vec_[2 * i_cur] = g0; f1.grad_vec_[2 * i_cur + 1] = g1;
       f1.landmark_vec_[i_cur] = new_point;
       f1.track_id_vec_[i_cur] = new_point->id();
-      new_point->obs_.push_back(Point::Obs{ frame1, i_cur });
+      new_point->addObservation(frame1, i_cur);
       f1.num_features_++;
       ++n_succeeded;
     } else {
@@ -2123,6 +2123,22 @@ void matchCandidatesFused(svoh_ctx* ctx, const FramePtr& frame, bool affine_est_
 }
 }  // namespace reprojector_utils
 
+// ---- Point::addObservation (point.cpp:41-58) ---------------------------------------
+void Point::addObservation(const FramePtr& frame, size_t feature_index)
+{
+  if (!frame) throw std::runtime_error("Point::addObservation: NULL frame");   // CHECK_NOTNULL
+  const int id = frame->id();
+  for (const Obs& o : obs_) {
+    const FramePtr f = o.frame.lock();
+    if (!f || f->id() != id) continue;
+    if (o.keypoint_index_ != feature_index)   // CHECK_EQ(it->keypoint_index_, feature_index)
+      throw std::runtime_error("Point::addObservation: frame " + std::to_string(id) + " observes point " + std::to_string(id_) + " at feature " +
+                               std::to_string(o.keypoint_index_) + " already, not at " + std::to_string(feature_index));
+    return;
+  }
+  obs_.push_back(Obs{ frame, feature_index });
+}
+
 // ---- structure optimisation -------------------------------------------------------
 int StructureBatch::gather(const Frame& frame, int max_n_pts)
 {
@@ -2214,7 +2230,7 @@ size_t upgradeSeedsToFeatures(const FramePtr& frame, int* next_point_id, std::ve
   for (size_t i = 0; i < n; ++i) {
     if (fr.landmark_vec_[i]) {
       // (corner / edgelet / map point, or a fixed landmark: either way) landmark_vec_[i]->addObservation(frame, i)
-      fr.landmark_vec_[i]->obs_.push_back(Point::Obs{ frame, i });
+      fr.landmark_vec_[i]->addObservation(frame, i);
     } else if (fr.seed_ref_vec_[i].keyframe) {
       Frame::SeedRef& ref = fr.seed_ref_vec_[i];
       Frame& kf = *ref.keyframe;
@@ -2231,21 +2247,22 @@ size_t upgradeSeedsToFeatures(const FramePtr& frame, int* next_point_id, std::ve
         point->id_ = (*next_point_id)++;
         kf.landmark_vec_[sid] = point;
         kf.track_id_vec_[sid] = point->id();
-        point->obs_.push_back(Point::Obs{ ref.keyframe, sid });
+        point->addObservation(ref.keyframe, sid);
       }
       fr.landmark_vec_[i] = point;
       fr.track_id_vec_[i] = point->id();
-      point->obs_.push_back(Point::Obs{ frame, i });
+      point->addObservation(frame, i);
       const uint8_t kt = kf.type_vec_[sid];
       if (is_corner(kt)) { kf.type_vec_[sid] = SVOH_FT_CORNER; fr.type_vec_[i] = SVOH_FT_CORNER; }
       else if (is_map_pt(kt)) { kf.type_vec_[sid] = SVOH_FT_MAPPOINT; fr.type_vec_[i] = SVOH_FT_MAPPOINT; }
       else if (is_edgelet(kt)) { kf.type_vec_[sid] = SVOH_FT_EDGELET; fr.type_vec_[i] = SVOH_FT_EDGELET; edgelets->push_back(i); }
       else throw std::runtime_error("upgradeSeedsToFeatures: Seed-Type not known");   // CHECK(false)
       ++update_count;
-      // (a self reference -- the harness' stand-in for the initialiser's landmarks -- is a reference like any other)
-      ref.keyframe.reset();
-      ref.seed_id = -1;
     }
+    // every feature, whichever arm it took, lets go of its seed (:906-908): a feature with a landmark may carry an old reference
+    // (a self reference -- the harness' stand-in for the initialiser's landmarks -- is a reference like any other)
+    fr.seed_ref_vec_[i].keyframe.reset();
+    fr.seed_ref_vec_[i].seed_id = -1;
   }
   return update_count;
 }

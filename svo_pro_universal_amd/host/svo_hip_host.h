@@ -451,6 +451,9 @@ struct Point {
   const svoh::Vec3& pos() const { return pos_; }
   int id() const { return id_; }
   bool getCloseViewObs(const svoh::Vec3& framepos, FramePtr& ref_frame, size_t& ref_feature_index) const;
+  // Point::addObservation (point.cpp:41-58): one observation per frame.  Nothing is added when a live observation of a frame with
+  // this frame's id is there already; if that one names another feature, std::runtime_error (the reference's CHECK_EQ).
+  void addObservation(const FramePtr& frame, size_t feature_index);
 };
 using PointPtr = std::shared_ptr<Point>;
 

@@ -491,8 +491,8 @@ double rescaleAndInitializePoints(const FramePtr& frame_cur, const FramePtr& fra
     new_point->pos_ = svoh::Vec3{ world[3 * i], world[3 * i + 1], world[3 * i + 2] };
     frame_cur->landmark_vec_.at(ic) = new_point;
     frame_ref->landmark_vec_.at(ir) = new_point;
-    new_point->obs_.push_back(Point::Obs{ frame_ref, ir });
-    new_point->obs_.push_back(Point::Obs{ frame_cur, ic });
+    new_point->addObservation(frame_ref, ir);
+    new_point->addObservation(frame_cur, ic);
   }
   return scale;
 }

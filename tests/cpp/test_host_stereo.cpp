@@ -158,6 +158,18 @@ int main(int argc, char** argv)
   for (size_t k = n_old; k < f0->num_features_; ++k) n_lm += f0->landmark_vec_[k] != nullptr;
   CHECK(n_lm == (size_t)o_succ);
   for (int k = 0; k < n_have; ++k) CHECK(f0->track_id_vec_[k] == 1000 + k);
+  // the rest of the keyframe step (frame_handler_stereo.cpp:149-162): both frames through upgradeSeedsToFeatures.  Every feature adds
+  // itself to its landmark, which holds that observation already (Point::addObservation, point.cpp:41-58): one observation per frame.
+  {
+    int next_point_id = 1 << 20;
+    std::vector<size_t> e0, e1;
+    CHECK(upgradeSeedsToFeatures(f1, &next_point_id, &e1) == 0 && upgradeSeedsToFeatures(f0, &next_point_id, &e0) == 0 && next_point_id == 1 << 20);
+    for (int s = 0; s < o_succ; ++s) {
+      const Point& lm = *f1->landmark_vec_[s];
+      CHECK(lm.obs_.size() == 2 && lm.obs_[0].frame.lock() == f0 && lm.obs_[0].keypoint_index_ == (size_t)om[s].i_ref && lm.obs_[1].frame.lock() == f1 &&
+            lm.obs_[1].keypoint_index_ == (size_t)s);
+    }
+  }
   // a second call has enough landmarks now when the target was reached: no effect
   if (o_succ == n_desired) {
     const size_t nf0 = f0->num_features_, nf1 = f1->num_features_;

@@ -478,8 +478,9 @@ def test_candidate_sort_with_packed_keys_is_the_reference_sort():
 
 def test_upgrade_seeds_to_features_host_half():
     """svo_hip::upgradeSeedsToFeatures (round 6; FrameHandlerBase::upgradeSeedsToFeatures, frame_handler_base.cpp:828-920) on a
-    hand-made keyframe / frame pair: points at the seeds' positions, types, observations, track ids, cleared seed references, the
-    list of upgraded edgelets, two features on one seed, a feature with a landmark of its own; removeObservationsOf
+    hand-made keyframe / frame pair: points at the seeds' positions, types, observations (one per frame), track ids, cleared seed
+    references, the list of upgraded edgelets, two features on one seed (refused, as the reference's CHECK_EQ does), a feature with a
+    landmark of its own and a left-over seed reference; removeObservationsOf
     (Map::removeKeyframe).  tests/cpp/host_upgrade_cpu, no GPU call."""
     import os, subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
