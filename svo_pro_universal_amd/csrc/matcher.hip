@@ -2901,8 +2901,24 @@ __global__ __launch_bounds__(kPkThreads) __attribute__((amdgpu_waves_per_eu(3)))
 // host side
 // ---------------------------------------------------------------------------
 
-// wide_allowed: the entry runs EQUIDISTANT | ATAN views (the blocking host-array forms of svoh_update_seeds_batch, svoh_match_direct_batch,
-// svoh_match_direct_batch_pixelwise and svoh_epipolar_match_batch); everything else refuses them, as the default says
+// Every entry below sends its batch through one staging block described by svoh_matcher_block.h (the layouts are there), checks
+// its svoh_feature_batch with check_feature_batch, resolves its frames with fill_view_table and launches inside launch_bracket.
+// Which entry runs EQUIDISTANT | ATAN views (the *_wide_kernel twins); everything else refuses them with SVOH_ERR_UNSUPPORTED.
+enum MatcherEntry { kEntryUpdateSeeds, kEntryMatchDirect, kEntryMatchPixelwise, kEntryEpipolar, kEntryUpdateSeedsEx, kEntrySeedChain };
+static bool wide_views_admitted(MatcherEntry entry, bool device_arrays, bool deferred_form)
+{
+  static const bool kWide[] = {
+    /* svoh_update_seeds_batch           */ true,
+    /* svoh_match_direct_batch           */ true,
+    /* svoh_match_direct_batch_pixelwise */ true,
+    /* svoh_epipolar_match_batch         */ true,
+    /* svoh_update_seeds_batch_ex        */ false,   // kept as it is: svo_hip.h says "NONE / RADTAN views only" of it
+    /* svoh_update_seeds_chain           */ false,   // the chain kernel has no wide twin
+  };
+  // ... and of those the blocking form over host arrays only; the staged form (run_matcher_staged) never asks
+  return kWide[entry] && !device_arrays && !deferred_form;
+}
+
 template <class View>
 static int fill_view(svoh_ctx* ctx, const svoh_frame_view& v, View* out, const char* what, bool pose_from_results_allowed = false,
                      bool wide_allowed = false)
@@ -2937,21 +2953,126 @@ static int fill_view(svoh_ctx* ctx, const svoh_frame_view& v, View* out, const c
   return SVOH_OK;
 }
 
-// The views of a launch once more for the *_wide_kernel twins, iff one of them has a wide camera (else `wviews` stays empty and
-// the launch runs the kernels it always ran).  After the narrow fill_view of every view has passed with wide_allowed.
-static int fill_wide_views(svoh_ctx* ctx, int n_ref_frames, const svoh_frame_view* ref_frames, int n_cur, const svoh_frame_view* cur_frame,
-                           std::vector<DevFrameViewWide>& wviews)
+// SVOH_BATCH_WHOLE_SETS: the units are the reference frames' features, frame after frame: where each frame's units begin
+static int begin_whole_sets(svoh_ctx* ctx, int n_ref_frames, const svoh_frame_view* ref_frames, DevFrameView* views, int n)
 {
-  bool wide = false;
-  for (int k = 0; k < n_ref_frames; ++k) wide = wide || !camera_is_narrow(ref_frames[k].cam);
-  for (int k = 0; k < n_cur; ++k) wide = wide || !camera_is_narrow(cur_frame[k].cam);
-  if (!wide) return SVOH_OK;
-  wviews.resize((size_t)n_ref_frames + n_cur);
-  for (int k = 0; k < n_ref_frames + n_cur; ++k) {
-    const int rc = k < n_ref_frames ? fill_view(ctx, ref_frames[k], &wviews[k], "reference frame", false, true)
-                                    : fill_view(ctx, cur_frame[k - n_ref_frames], &wviews[k], "current frame", false, true);
+  long long begin = 0;
+  for (int k = 0; k < n_ref_frames; ++k) {
+    SVOH_REQUIRE(ctx, ref_frames[k].features != 0, "SVOH_BATCH_WHOLE_SETS: a reference frame has no resident columns (svoh_frame_view::features)");
+    views[k].unit_begin = (int32_t)begin; begin += views[k].feat_n;
+  }
+  SVOH_REQUIRE(ctx, begin == n, "SVOH_BATCH_WHOLE_SETS: the reference frames' resident sets do not add up to the batch's n");
+  return SVOH_OK;
+}
+
+// What an entry asks of its frames ...
+struct ViewRules {
+  const char* cur_what;     // what the frames behind the reference frames are called in an error
+  bool wide;                // EQUIDISTANT | ATAN views are admitted (wide_views_admitted)
+  bool pose_from_results;   // a current view may take its pose from the pose batch in flight (svoh_frame_view::pose_result_index_plus1)
+  bool resident;            // every reference frame needs resident columns (the batch names its features by feature_index)
+  bool whole_sets;          // SVOH_BATCH_WHOLE_SETS: n_units are the reference frames' sets, frame after frame (begin_whole_sets)
+  // The search level is chosen up to the reference pyramid's top (patch_warp.cpp:97-110) and then read from the current frame: every
+  // current frame needs as many levels.  Reported of frame k ahead of what is wrong with frame k + 1 (ByFrame), or once every frame
+  // is resolved (Last: the direct / seed batches' order); the chain compares each chain with its own reference frame itself.
+  enum { kLevelsNotHere, kLevelsByFrame, kLevelsLast } levels;
+};
+// ... and what resolving them yields besides the table
+struct ViewTable {
+  int ref_levels = 0, max_w = 1, max_h = 1;   // the reference frames' deepest pyramid and largest level 0 (bins of the packed seed update)
+  bool pose_from_results = false;
+  std::vector<DevFrameViewWide> wide;         // the same table for the *_wide_kernel twins, iff one of the views has a wide camera
+};
+
+// The view table of a launch: the reference frames, then the current (or chain) frames, into views[n_ref_frames + n_cur].
+static int fill_view_table(svoh_ctx* ctx, const ViewRules& r, int n_ref_frames, const svoh_frame_view* ref_frames, int n_cur,
+                           const svoh_frame_view* cur_frames, int n_units, DevFrameView* views, ViewTable& t)
+{
+  const char* const few_levels = "current frame has fewer pyramid levels than a reference frame";
+  bool any_wide = false;
+  for (int k = 0; k < n_ref_frames; ++k) {
+    const int rc = fill_view(ctx, ref_frames[k], &views[k], "reference frame", false, r.wide);
+    if (rc != SVOH_OK) return rc;
+    t.ref_levels = std::max(t.ref_levels, (int)views[k].n_levels);
+    t.max_w = std::max(t.max_w, (int)views[k].lv[0].w); t.max_h = std::max(t.max_h, (int)views[k].lv[0].h);
+    SVOH_REQUIRE(ctx, !r.resident || ref_frames[k].features != 0, "a reference frame of a batch with feature_index has no resident columns (svoh_frame_view::features)");
+    any_wide = any_wide || !camera_is_narrow(ref_frames[k].cam);
+  }
+  for (int k = 0; k < n_cur; ++k) {
+    const DevFrameView& v = views[n_ref_frames + k];
+    const int rc = fill_view(ctx, cur_frames[k], &views[n_ref_frames + k], r.cur_what, r.pose_from_results, r.wide);
+    if (rc != SVOH_OK) return rc;
+    if (r.levels == ViewRules::kLevelsByFrame) SVOH_REQUIRE(ctx, v.n_levels >= t.ref_levels, few_levels);
+    SVOH_REQUIRE(ctx, v.pose_result_index_plus1 >= 0 && v.pose_result_index_plus1 <= ctx->n_pose_results, "pose_result_index_plus1: the pose batch in flight has no such result");
+    t.pose_from_results = t.pose_from_results || v.pose_result_index_plus1 > 0;
+    any_wide = any_wide || !camera_is_narrow(cur_frames[k].cam);
+  }
+  if (any_wide) {   // (every view has passed fill_view with r.wide)
+    t.wide.resize((size_t)n_ref_frames + n_cur);
+    for (int k = 0; k < n_ref_frames + n_cur; ++k) {
+      const int rc = k < n_ref_frames ? fill_view(ctx, ref_frames[k], &t.wide[k], "reference frame", false, true)
+                                      : fill_view(ctx, cur_frames[k - n_ref_frames], &t.wide[k], r.cur_what, false, true);
+      if (rc != SVOH_OK) return rc;
+    }
+  }
+  if (r.whole_sets) {
+    const int rc = begin_whole_sets(ctx, n_ref_frames, ref_frames, views, n_units);
     if (rc != SVOH_OK) return rc;
   }
+  if (r.levels == ViewRules::kLevelsLast)
+    for (int k = 0; k < n_cur; ++k) SVOH_REQUIRE(ctx, views[n_ref_frames + k].n_levels >= t.ref_levels, few_levels);
+  return SVOH_OK;
+}
+
+// What an entry admits in its svoh_feature_batch, and what it says when it does not
+struct BatchRules {
+  bool device_arrays;    // SVOH_MEM_DEVICE beside SVOH_MEM_HOST (the kernels range-check a device batch's indices themselves)
+  bool whole_sets;       // SVOH_BATCH_WHOLE_SETS, then over device arrays and outside a deferred section
+  bool cur_idx;          // cur_frame_idx may be given ...
+  bool cur_idx_by_unit;  // ... and a bad one of unit i is reported ahead of what is wrong with unit i + 1 (else behind every ref_frame_idx / level)
+  const char* bad_mem_space;
+  const char* bad_feature_index;
+  const char* bad_layout;
+};
+static const char* const kStagedOnlyFeatureIndex = "feature_index: staged batches only (svoh_matcher_stage with SVOH_STAGE_RESIDENT_COLUMNS)";
+static const char* const kWholeSetsLayout = "svoh_feature_batch::layout: SVOH_BATCH_WHOLE_SETS is for seed batches over resident columns, staged (svoh_matcher_stage) or with device arrays";
+static const BatchRules kDirectBatchRules = { true, false, true, false, "bad mem_space", kStagedOnlyFeatureIndex, kWholeSetsLayout };
+static const BatchRules kSeedBatchRules = { true, true, true, false, "bad mem_space", kStagedOnlyFeatureIndex, kWholeSetsLayout };
+static const BatchRules kEpipolarBatchRules = { true, false, true, true, "bad mem_space", kStagedOnlyFeatureIndex,
+  "svoh_feature_batch::layout: SVOH_BATCH_WHOLE_SETS is for staged seed batches over resident columns" };
+static const char* const kChainBatchForm = "svoh_update_seeds_chain: SVOH_BATCH_UNITS without feature_index and cur_frame_idx (the chains name the current frames)";
+static const BatchRules kChainBatchRules = { false, false, false, false, "svoh_update_seeds_chain: host arrays only (SVOH_MEM_HOST)", kChainBatchForm, kChainBatchForm };
+
+// The checks of a svoh_feature_batch that is not a staged one.  An entry has checks of its own between them, so it asks in up to
+// three steps: the batch's form (others_given: the entry's further required arrays, reported as a NULL feature array too), the
+// ranges of its indices, and -- with the view table -- its levels against the reference pyramids.  A device batch has form only.
+enum { kBatchForm = 1, kBatchRanges = 2, kBatchLevels = 4 };
+static int check_feature_batch(svoh_ctx* ctx, const BatchRules& r, int what, const svoh_feature_batch* fb, int n_ref_frames, int n_cur,
+                               bool others_given = true, const DevFrameView* views = nullptr)
+{
+  const int n = fb->n;
+  if (what & kBatchForm) {
+    SVOH_REQUIRE(ctx, fb->mem_space == SVOH_MEM_HOST || (r.device_arrays && fb->mem_space == SVOH_MEM_DEVICE), r.bad_mem_space);
+    SVOH_REQUIRE(ctx, !fb->feature_index, r.bad_feature_index);
+    const bool whole_sets = fb->layout == SVOH_BATCH_WHOLE_SETS;
+    SVOH_REQUIRE(ctx, fb->layout == SVOH_BATCH_UNITS || (whole_sets && r.whole_sets && fb->mem_space == SVOH_MEM_DEVICE && !ctx->matcher_deferred), r.bad_layout);
+    SVOH_REQUIRE(ctx, r.cur_idx || !fb->cur_frame_idx, r.bad_layout);
+    SVOH_REQUIRE(ctx, fb->type && (whole_sets || (fb->ref_frame_idx && fb->px && fb->f && fb->grad && fb->level)) && others_given, "NULL feature array");
+  }
+  if (fb->mem_space != SVOH_MEM_HOST) return SVOH_OK;
+  if (what & kBatchRanges) {
+    const int32_t* const cur_idx = fb->cur_frame_idx;
+    for (int i = 0; i < n; ++i) {
+      SVOH_REQUIRE(ctx, fb->ref_frame_idx[i] >= 0 && fb->ref_frame_idx[i] < n_ref_frames, "ref_frame_idx out of range");
+      SVOH_REQUIRE(ctx, fb->level[i] >= 0 && fb->level[i] < SVOH_MAX_LEVELS, "feature level out of range");
+      if (cur_idx && r.cur_idx_by_unit) SVOH_REQUIRE(ctx, cur_idx[i] >= 0 && cur_idx[i] < n_cur, "cur_frame_idx out of range");
+    }
+    if (cur_idx && !r.cur_idx_by_unit)
+      for (int i = 0; i < n; ++i) SVOH_REQUIRE(ctx, cur_idx[i] >= 0 && cur_idx[i] < n_cur, "cur_frame_idx out of range");
+  }
+  if (what & kBatchLevels)
+    for (int i = 0; i < n; ++i)
+      SVOH_REQUIRE(ctx, fb->level[i] < views[fb->ref_frame_idx[i]].n_levels, "feature level beyond the reference pyramid");
   return SVOH_OK;
 }
 
@@ -2966,19 +3087,32 @@ static MatcherArgsWide widen_args(const MatcherArgs& a)
   return w;
 }
 
-struct Staging {
-  std::vector<std::pair<const void*, size_t>> in;   // host source, bytes
-  std::vector<size_t> off;
-  size_t total = 0;
-  size_t add(const void* p, size_t bytes)
-  {
-    const size_t o = total;
-    in.emplace_back(p, bytes);
-    off.push_back(o);
-    total = (total + bytes + 63) & ~(size_t)63;
-    return o;
+// The kernel arguments of a batch whose block `b` lies at `d` on the device: every pointer at its column, at the caller's own
+// array for a device batch, NULL where the block has no such column (MatcherBlock::at); `c`: the chain's as well
+static MatcherArgs matcher_args(const MatcherBlock& b, uint8_t* d, const svoh_matcher_options* mopt, const svoh_depth_filter_options* dopt,
+                                int n, int n_ref_frames, int n_cur_frames, SeedChainArgs* c = nullptr)
+{
+  const auto bind = [&](auto& p, MatcherSlot s) { p = static_cast<std::remove_reference_t<decltype(p)>>(b.at(d, s)); };
+  MatcherArgs a;
+  memset(&a, 0, sizeof a);
+  a.mopt = *mopt;
+  if (dopt) a.dopt = *dopt;
+  a.n = n; a.n_ref_frames = n_ref_frames; a.n_cur_frames = n_cur_frames;
+  bind(a.ref_frames, kSlotViews);
+  a.cur_frame = a.ref_frames + n_ref_frames;
+  bind(a.T_cur_ref, kSlotTCurRef);
+  bind(a.ref_frame_idx, kSlotRefIdx); bind(a.cur_frame_idx, kSlotCurIdx);
+  bind(a.px, kSlotPx); bind(a.f, kSlotF); bind(a.grad, kSlotGrad); bind(a.level, kSlotLevel); bind(a.type, kSlotType);
+  bind(a.depth, kSlotDepth); bind(a.landmark_xyz, kSlotLandmark); bind(a.d_inv, kSlotDInv);
+  bind(a.px_cur, kSlotPxCur); bind(a.state, kSlotState);
+  bind(a.result, kSlotResult); bind(a.f_cur, kSlotFCur); bind(a.search_level, kSlotSearchLevel); bind(a.h_inv, kSlotHInv);
+  bind(a.A_cur_ref, kSlotA); bind(a.success, kSlotSuccess); bind(a.depth_out, kSlotDepthOut);
+  if (c) {
+    bind(c->chain_begin, kSlotChainBegin); bind(c->chain_idx, kSlotChainIdx);
+    bind(c->steps_succeeded, kSlotStepsOk); bind(c->step_result, kSlotStepResult); bind(c->step_success, kSlotStepSuccess);
   }
-};
+  return a;
+}
 
 __global__ void count_success_kernel(const uint8_t* success, int n, int* out)
 {
@@ -2988,21 +3122,54 @@ __global__ void count_success_kernel(const uint8_t* success, int n, int* out)
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
 }
 
-// The kernels of one batch in geometry g8 (0 one lane per unit, 1 eight lanes, 2 packed, 3 one wave per unit), on the
-// context's stream; max_w x max_h = the largest reference frame (bins of the packed seed update).
-// wide: the views are DevFrameViewWide (fill_wide_views) and g8 is the twin's one geometry: eight lanes per unit for the
-// seed update (1), one lane per unit for the direct matcher (0, which has both warps).
-static int launch_matcher_kernels(svoh_ctx* ctx, bool seeds, int g8, MatcherArgs& a, int n, int n_ref_frames, int max_w, int max_h,
+// ---- which geometry a launch gets: one small rule per entry ------------------------------------------------------------
+// Small batches: eight lanes per unit (a launch is as slow as its slowest lane, and eight lanes get a unit done ~3x sooner);
+// large batches: the packed kernels (fewer instructions per unit).  The knob SVOH_MATCHER_G8 (read when the context is made)
+// takes the place of that choice by size; a value that names no geometry means one lane per unit.
+static MatcherGeometry geometry_or_knob(const svoh_ctx* ctx, MatcherGeometry by_size)
+{
+  const int g = SvohKnobs::or_default(ctx->knobs.matcher_g8, (int)by_size);
+  return (g < 0 || g > 3) ? kGeomOneLane : (MatcherGeometry)g;
+}
+// a direct or seed batch (deferred: queued in a deferred section, from host arrays or staged)
+static MatcherGeometry batch_geometry(const svoh_ctx* ctx, int n, bool seeds, bool deferred, bool pixelwise, bool device_whole_sets, bool wide)
+{
+  MatcherGeometry g = geometry_or_knob(ctx, n <= kG8MaxUnits ? kGeomEightLanes : kGeomPacked);
+  // one wave per unit: the seed update only, on request (its scans are short); the direct matcher has no scan
+  if (g == kGeomOneWave && (!seeds || deferred)) g = kGeomEightLanes;
+  if (pixelwise) g = kGeomOneLane;         // the pixelwise warp exists with one lane per unit only
+  if (device_whole_sets) g = kGeomPacked;  // a device batch over whole sets: the packed geometry reads the resident columns itself
+  if (wide) g = seeds ? kGeomEightLanes : kGeomOneLane;   // a wide launch: the twin's one geometry (the direct one has both warps), whatever the size and the knob say
+  return g;
+}
+// the plain epipolar matches: one wave per unit, the scan 64 steps at a time, is what a long search (the stereo seam's 500 steps)
+// gets while the batch leaves the device room for a wave per feature (a launch is as slow as its slowest feature: 8 rounds instead of 63)
+static MatcherGeometry epipolar_geometry(const svoh_ctx* ctx, int n, int max_epi_search_steps, bool wide)
+{
+  constexpr int kW64MaxUnits = 16384;
+  if (wide) return kGeomOneWave;   // the twin's one geometry, whatever the size and the knob say
+  return geometry_or_knob(ctx, n <= kG8MaxUnits ? ((max_epi_search_steps > 128 && n <= kW64MaxUnits) ? kGeomOneWave : kGeomEightLanes) : kGeomPacked);
+}
+// the seed chain: eight lanes per unit unless the knob asks for one lane or one wave; there is no packed form
+static MatcherGeometry chain_geometry(const svoh_ctx* ctx)
+{
+  const int g = SvohKnobs::or_default(ctx->knobs.matcher_g8, (int)kGeomEightLanes);
+  return g == kGeomOneLane ? kGeomOneLane : (g == kGeomOneWave ? kGeomOneWave : kGeomEightLanes);
+}
+
+// The kernels of one direct or seed batch in geometry g, on the context's stream (inside launch_bracket); max_w x max_h = the
+// largest reference frame (bins of the packed seed update).
+// wide: the views are DevFrameViewWide (ViewTable::wide) and g is the twin's one geometry (batch_geometry).
+static int launch_matcher_kernels(svoh_ctx* ctx, bool seeds, MatcherGeometry g, MatcherArgs& a, int n, int n_ref_frames, int max_w, int max_h,
                                   bool wide = false)
 {
-  const int units_per_block = g8 == 1 ? 8 : (g8 == 3 ? 1 : 64);
-  const dim3 grid((unsigned)((n + units_per_block - 1) / units_per_block)), block(64);
+  const dim3 grid((unsigned)((n + units_per_block(g) - 1) / units_per_block(g))), block(64);
   if (wide) {
     const MatcherArgsWide aw = widen_args(a);
     if (seeds) hipLaunchKernelGGL(update_seeds_wide_kernel<1>, grid, block, 0, ctx->stream, aw);
     else hipLaunchKernelGGL(match_direct_wide_kernel<false>, grid, block, 0, ctx->stream, aw);
   } else if (seeds) {
-    if (g8 == 2) {
+    if (g == kGeomPacked) {
       if (max_w < 1) max_w = 1;
       if (max_h < 1) max_h = 1;
       const int tiles_x = (max_w + (1 << kBinShiftX) - 1) >> kBinShiftX, tiles_y = (max_h + (1 << kBinShiftY) - 1) >> kBinShiftY;
@@ -3051,138 +3218,202 @@ static int launch_matcher_kernels(svoh_ctx* ctx, bool seeds, int g8, MatcherArgs
       if (rec_out) hipLaunchKernelGGL(seed_unsort_kernel, gb, dim3(256), 0, ctx->stream, a, pos_of, static_cast<const SeedRecOut*>(rec_out),
                                       hist_ptr, hist_keys);
     }
-    else if (g8 == 3) hipLaunchKernelGGL(update_seeds_kernel<3>, grid, block, 0, ctx->stream, a);
-    else if (g8) hipLaunchKernelGGL(update_seeds_kernel<1>, grid, block, 0, ctx->stream, a);
+    else if (g == kGeomOneWave) hipLaunchKernelGGL(update_seeds_kernel<3>, grid, block, 0, ctx->stream, a);
+    else if (g == kGeomEightLanes) hipLaunchKernelGGL(update_seeds_kernel<1>, grid, block, 0, ctx->stream, a);
     else hipLaunchKernelGGL(update_seeds_kernel<0>, grid, block, 0, ctx->stream, a);
   } else {
-    if (g8 == 2) hipLaunchKernelGGL(match_packed_kernel<true>, dim3((unsigned)((n + kPkThreads - 1) / kPkThreads)), dim3(kPkThreads), 0, ctx->stream, a);
-    else if (g8) hipLaunchKernelGGL(match_direct_kernel<true>, grid, block, 0, ctx->stream, a);
+    if (g == kGeomPacked) hipLaunchKernelGGL(match_packed_kernel<true>, dim3((unsigned)((n + kPkThreads - 1) / kPkThreads)), dim3(kPkThreads), 0, ctx->stream, a);
+    else if (g != kGeomOneLane) hipLaunchKernelGGL(match_direct_kernel<true>, grid, block, 0, ctx->stream, a);
     else hipLaunchKernelGGL(match_direct_kernel<false>, grid, block, 0, ctx->stream, a);
   }
-  SVOH_HIP_TRY(ctx, hipGetLastError());
   return SVOH_OK;
+}
+
+// What stands around every matcher launch: the work counters are reset, the per-unit counts get their room (*unit_counts, for
+// the kernel arguments), `before` queues what must run ahead of the timed region, `launch` the kernels between the event pair
+// (when kernel timing is on), and the per-unit counts are added up behind them.
+struct NothingBefore { int operator()() const { return SVOH_OK; } };
+template <class Launch, class Before = NothingBefore>
+static int launch_bracket(svoh_ctx* ctx, size_t n_units, unsigned int** unit_counts, Launch&& launch, Before&& before = Before())
+{
+  unsigned long long* dummy;
+  int rc = reset_counters(ctx, &dummy);
+  if (rc == SVOH_OK) rc = reserve_unit_counts(ctx, n_units, unit_counts);
+  if (rc == SVOH_OK) rc = before();
+  if (rc != SVOH_OK) return rc;
+  if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_start, ctx->stream));
+  rc = launch();
+  if (rc != SVOH_OK) return rc;
+  SVOH_HIP_TRY(ctx, hipGetLastError());
+  if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_stop, ctx->stream));
+  ctx->misc_timed = ctx->timing_on(); ctx->misc_launched = true;
+  return reduce_unit_counts(ctx, n_units);
+}
+
+// A batch of a deferred section, from host arrays or staged: the launch waits for svoh_matcher_flush / _collect, where a direct and
+// a seed batch of the same per-unit geometry go out as ONE kernel (match_mixed_kernel).  Remembered: the arguments, the output area
+// [b.in_total, out_end) that the packed geometry wants zeroed, and the copy of the results back to the pinned block.
+static void queue_deferred(svoh_ctx* ctx, int kind, const MatcherArgs& a, MatcherGeometry g, const MatcherBlock& b, uint8_t* h, uint8_t* d,
+                           size_t out_end, const ViewTable& t, uint64_t cur_frame_handle)
+{
+  svoh_ctx::DeferredLaunch& dl = ctx->matcher_deferred_launch[kind];
+  dl.args.assign(reinterpret_cast<const uint8_t*>(&a), reinterpret_cast<const uint8_t*>(&a) + sizeof a);
+  dl.n = a.n; dl.g8 = g; dl.valid = true; dl.max_w = t.max_w; dl.max_h = t.max_h;
+  dl.d_block = d; dl.out_off = b.in_total; dl.out_bytes = out_end - b.in_total;
+  dl.d2h_dst = h + b.back_from; dl.d2h_src = d + b.back_from; dl.d2h_bytes = b.end - b.back_from;
+  dl.views_h = h + b.off(kSlotViews); dl.views_d = d + b.off(kSlotViews); dl.n_ref = a.n_ref_frames; dl.n_cur = a.n_cur_frames;
+  dl.cur_frame_handle = cur_frame_handle;
+  dl.pose_from_results = t.pose_from_results; dl.d_pose_results = t.pose_from_results ? ctx->d_pose_results : nullptr; dl.n_pose_results = ctx->n_pose_results;
+  dl.d_fidx = b.has(kSlotFeatIdx) ? d + b.off(kSlotFeatIdx) : nullptr;
+}
+
+// ---- a matcher batch staged in place (svoh_matcher_stage, SVOH_MEM_STAGED) -------------------------------------------
+// The caller -- the lock-step front end of many camera streams, with one host thread per few streams -- writes a batch's
+// inputs straight into the section's page-locked block and reads its outputs from there: no concatenation of per-stream
+// arrays, no staging copy inside the call, no copy to caller arrays at collect (at 32 streams those were 3 - 5 MB each way
+// per batch, on ONE thread).  The layout: layout_matcher_stage (svoh_matcher_block.h).
+
+// The frames the last staged batch asked for, [n_ref_frames | reference views | current views] as the caller wrote them: compared
+// with this call's (store = false) or replaced by them
+static bool staged_views_key(svoh_ctx* ctx, int n_ref_frames, const svoh_frame_view* ref_frames, int n_cur, const svoh_frame_view* cur_frame, bool store)
+{
+  const void* const part[3] = { &n_ref_frames, ref_frames, cur_frame };
+  const size_t bytes[3] = { sizeof(int), sizeof(svoh_frame_view) * (size_t)n_ref_frames, sizeof(svoh_frame_view) * (size_t)n_cur };
+  std::vector<uint8_t>& key = ctx->staged_views_key;
+  if (store) key.resize(bytes[0] + bytes[1] + bytes[2]);
+  else if (key.size() != bytes[0] + bytes[1] + bytes[2]) return false;
+  uint8_t* at = key.data();
+  for (int k = 0; k < 3; at += bytes[k++]) {
+    if (store) memcpy(at, part[k], bytes[k]);
+    else if (memcmp(at, part[k], bytes[k]) != 0) return false;
+  }
+  return true;
 }
 
 static int run_matcher_staged(svoh_ctx* ctx, bool seeds, const svoh_matcher_options* mopt, const svoh_depth_filter_options* dopt,
                               int n_ref_frames, const svoh_frame_view* ref_frames, const svoh_frame_view* cur_frame,
-                              const svoh_feature_batch* fb, const double* depth, double* px_cur, int32_t* result, double* f_cur,
-                              int32_t* search_level, double* h_inv, double* A_cur_ref, double* state, uint8_t* success, int32_t* n_success);
-
-static int run_matcher(svoh_ctx* ctx, bool seeds, const svoh_matcher_options* mopt, const svoh_depth_filter_options* dopt,
-                       int n_ref_frames, const svoh_frame_view* ref_frames, const svoh_frame_view* cur_frame,
-                       const svoh_feature_batch* fb, const double* depth, double* px_cur, int32_t* result, double* f_cur,
-                       int32_t* search_level, double* h_inv, double* A_cur_ref, double* state, uint8_t* success,
-                       int32_t* n_success, const double* landmark_xyz = nullptr, bool wide_entry = false)
+                              const svoh_feature_batch* fb, const MatcherArrays& c)
 {
-  if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  SVOH_REQUIRE(ctx, mopt && ref_frames && cur_frame && fb && n_ref_frames >= 1, "NULL argument");
-  SVOH_REQUIRE(ctx, !landmark_xyz || (!seeds && !ctx->matcher_deferred), "the pixelwise warp: direct matches only, outside a deferred section");
+  const int kind = seeds ? 1 : 0;
+  svoh_ctx::MatcherStage& st = ctx->matcher_stage[kind];
+  const MatcherBlock& b = st.block;
+  SVOH_REQUIRE(ctx, ctx->matcher_deferred, "a staged batch lives in a deferred section (svoh_matcher_begin_deferred)");
+  SVOH_REQUIRE(ctx, st.valid, "no staged block of this kind: svoh_matcher_stage first");
+  SVOH_REQUIRE(ctx, !ctx->matcher_deferred_used[kind], "one batch of each kind per deferred section: collect first");
   const int n = fb->n;
-  if (n_success) *n_success = 0;
-  if (n <= 0) return SVOH_OK;
-  if (fb->mem_space == SVOH_MEM_STAGED) {
-    SVOH_REQUIRE(ctx, !landmark_xyz, "the pixelwise warp has no staged form");
-    return run_matcher_staged(ctx, seeds, mopt, dopt, n_ref_frames, ref_frames, cur_frame, fb, depth, px_cur, result, f_cur, search_level,
-                              h_inv, A_cur_ref, state, success, n_success);
-  }
-  SVOH_REQUIRE(ctx, fb->mem_space == SVOH_MEM_HOST || fb->mem_space == SVOH_MEM_DEVICE, "bad mem_space");
-  SVOH_REQUIRE(ctx, !fb->feature_index, "feature_index: staged batches only (svoh_matcher_stage with SVOH_STAGE_RESIDENT_COLUMNS)");
-  // SVOH_BATCH_WHOLE_SETS on a DEVICE batch: the seeds' state / type / current-frame index live in the caller's device arrays in the
-  // sets' order, the columns are the reference frames' resident ones; always the packed geometry (which walks the tile-ordered copies)
+  PinnedBuffer& hbuf = seeds ? ctx->h_match_seeds : ctx->h_match_direct;
+  DevBuffer& dbuf = seeds ? ctx->d_match_seeds : ctx->d_match_direct;
+  uint8_t* h = static_cast<uint8_t*>(hbuf.ptr);
+  uint8_t* d = static_cast<uint8_t*>(dbuf.ptr);
+  SVOH_REQUIRE(ctx, n == st.n && h && d && hbuf.cap >= b.total && dbuf.cap >= b.total, "not the batch that was staged (n differs)");
+  const int n_cur = fb->n_cur_frames > 0 ? fb->n_cur_frames : 1;
+  SVOH_REQUIRE(ctx, n_ref_frames + n_cur <= st.max_views, "more frames than the staged block has room for (max_frame_views)");
+  // the arrays must be the staged ones (is: what svoh_matcher_stage handed out for the slot, NULL where none; opt: that, or not given)
+  const auto is = [&](const void* p, MatcherSlot s) { return p == b.staged(h, s); };
+  const auto opt = [&](const void* p, MatcherSlot s) { return !p || p == b.staged(h, s); };
+  SVOH_REQUIRE(ctx, is(fb->ref_frame_idx, kSlotRefIdx) && is(fb->cur_frame_idx, kSlotCurIdx) && is(fb->type, kSlotType),
+               "a staged batch's feature arrays must be the pointers svoh_matcher_stage handed out");
   const bool whole_sets = fb->layout == SVOH_BATCH_WHOLE_SETS;
-  SVOH_REQUIRE(ctx, fb->layout == SVOH_BATCH_UNITS || (whole_sets && seeds && fb->mem_space == SVOH_MEM_DEVICE && !ctx->matcher_deferred),
-               "svoh_feature_batch::layout: SVOH_BATCH_WHOLE_SETS is for seed batches over resident columns, staged (svoh_matcher_stage) or with device arrays");
-  const bool on_device = fb->mem_space == SVOH_MEM_DEVICE;
-  SVOH_REQUIRE(ctx, fb->type && (whole_sets || (fb->ref_frame_idx && fb->px && fb->f && fb->grad && fb->level)), "NULL feature array");
-  if (seeds) SVOH_REQUIRE(ctx, dopt && state && success, "NULL seed argument");
-  else SVOH_REQUIRE(ctx, depth && px_cur && result, "NULL match argument");
-  const int n_cur = (fb->cur_frame_idx && fb->n_cur_frames > 0) ? fb->n_cur_frames : 1;
-  if (!on_device) {
-    for (int i = 0; i < n; ++i) {
-      SVOH_REQUIRE(ctx, fb->ref_frame_idx[i] >= 0 && fb->ref_frame_idx[i] < n_ref_frames, "ref_frame_idx out of range");
-      SVOH_REQUIRE(ctx, fb->level[i] >= 0 && fb->level[i] < SVOH_MAX_LEVELS, "feature level out of range");
-    }
-    if (fb->cur_frame_idx)
-      for (int i = 0; i < n; ++i)
-        SVOH_REQUIRE(ctx, fb->cur_frame_idx[i] >= 0 && fb->cur_frame_idx[i] < n_cur, "cur_frame_idx out of range");
+  SVOH_REQUIRE(ctx, fb->layout == SVOH_BATCH_UNITS || whole_sets, "svoh_feature_batch::layout: SVOH_BATCH_UNITS or SVOH_BATCH_WHOLE_SETS");
+  SVOH_REQUIRE(ctx, !whole_sets || (seeds && st.resident), "SVOH_BATCH_WHOLE_SETS: seed batches staged with SVOH_STAGE_RESIDENT_COLUMNS");
+  SVOH_REQUIRE(ctx, is(fb->feature_index, kSlotFeatIdx) && is(fb->px, kSlotPx) && is(fb->f, kSlotF) && is(fb->grad, kSlotGrad) && is(fb->level, kSlotLevel),
+               st.resident ? "a batch staged with SVOH_STAGE_RESIDENT_COLUMNS names its features by feature_index (the staged pointer); px / f / grad / level are NULL"
+                           : "a staged batch's feature arrays must be the pointers svoh_matcher_stage handed out");
+  if (seeds) {
+    SVOH_REQUIRE(ctx, dopt && is(c.state, kSlotState) && is(c.success, kSlotSuccess), "a staged seed batch's state / success must be the staged pointers");
+    SVOH_REQUIRE(ctx, opt(c.result, kSlotResult), "result: not the staged pointer");
+    SVOH_REQUIRE(ctx, st.want_outputs || (!c.px_cur && !c.f_cur && !c.search_level && !c.A_cur_ref), "the block was staged without match outputs");
+    SVOH_REQUIRE(ctx, opt(c.px_cur, kSlotPxCur) && opt(c.f_cur, kSlotFCur) && opt(c.search_level, kSlotSearchLevel) && opt(c.A_cur_ref, kSlotA),
+                 "match outputs: not the staged pointers");
+  } else {
+    SVOH_REQUIRE(ctx, is(c.depth, kSlotDepth) && is(c.px_cur, kSlotPxCur) && is(c.result, kSlotResult), "a staged direct batch's depth / px_cur / result must be the staged pointers");
+    SVOH_REQUIRE(ctx, opt(c.f_cur, kSlotFCur) && opt(c.search_level, kSlotSearchLevel) && opt(c.h_inv, kSlotHInv) && opt(c.A_cur_ref, kSlotA),
+                 "match outputs: not the staged pointers");
   }
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   SVOH_ALIGN_JOIN(ctx);
-
-  // EQUIDISTANT | ATAN views: the blocking host-array form of an entry that passes wide_entry only (device arrays and a
-  // deferred section keep refusing them, as the staged form does)
-  const bool wide_allowed = wide_entry && !on_device && !ctx->matcher_deferred;
-  std::vector<DevFrameView> views((size_t)n_ref_frames + n_cur);
-  for (int k = 0; k < n_ref_frames; ++k) {
-    int rc = fill_view(ctx, ref_frames[k], &views[k], "reference frame", false, wide_allowed);
+  DevFrameView* views = static_cast<DevFrameView*>(b.staged(h, kSlotViews));
+  ViewTable t;
+  // the same frames as the last staged batch asked for, none released since: that batch's table (a reprojection's direct and
+  // seed batch name the same keyframes and current frames; a table of 60 views is 10 us of look-ups on the caller's thread)
+  bool reuse = ctx->staged_views_generation == ctx->handle_generation && staged_views_key(ctx, n_ref_frames, ref_frames, n_cur, cur_frame, false);
+  for (int k = 0; k < n_cur && reuse; ++k) reuse = cur_frame[k].pose_result_index_plus1 == 0;   // (those go through the checks below)
+  if (reuse) {
+    memcpy(views, ctx->staged_views_resolved.data(), sizeof(DevFrameView) * (size_t)(n_ref_frames + n_cur));
+    t.ref_levels = ctx->staged_views_ref_levels; t.max_w = ctx->staged_views_max_w; t.max_h = ctx->staged_views_max_h;
+    if (st.resident) for (int k = 0; k < n_ref_frames; ++k) SVOH_REQUIRE(ctx, ref_frames[k].features != 0, "a reference frame of a batch with feature_index has no resident columns (svoh_frame_view::features)");
+  } else {
+    const ViewRules rules = { "current frame", false, seeds && ctx->in_pose_hook, st.resident, false, ViewRules::kLevelsByFrame };
+    const int rc = fill_view_table(ctx, rules, n_ref_frames, ref_frames, n_cur, cur_frame, n, views, t);
     if (rc != SVOH_OK) return rc;
-  }
-  for (int k = 0; k < n_cur; ++k) {
-    int rc = fill_view(ctx, cur_frame[k], &views[n_ref_frames + k], "current frame", false, wide_allowed);
-    if (rc != SVOH_OK) return rc;
-  }
-  std::vector<DevFrameViewWide> wviews;
-  {
-    const int rc = fill_wide_views(ctx, n_ref_frames, ref_frames, n_cur, cur_frame, wviews);
-    if (rc != SVOH_OK) return rc;
-  }
-  const bool wide = !wviews.empty();
-  if (whole_sets) {
-    long long begin = 0;
-    for (int k = 0; k < n_ref_frames; ++k) {
-      SVOH_REQUIRE(ctx, ref_frames[k].features != 0, "SVOH_BATCH_WHOLE_SETS: a reference frame has no resident columns (svoh_frame_view::features)");
-      views[k].unit_begin = (int32_t)begin; begin += views[k].feat_n;
+    ctx->staged_views_generation = ~0ull;
+    if (!t.pose_from_results) {
+      staged_views_key(ctx, n_ref_frames, ref_frames, n_cur, cur_frame, true);
+      ctx->staged_views_resolved.assign(reinterpret_cast<const uint8_t*>(views), reinterpret_cast<const uint8_t*>(views) + sizeof(DevFrameView) * (size_t)(n_ref_frames + n_cur));
+      ctx->staged_views_ref_levels = t.ref_levels; ctx->staged_views_max_w = t.max_w; ctx->staged_views_max_h = t.max_h;
+      ctx->staged_views_generation = ctx->handle_generation;
     }
-    SVOH_REQUIRE(ctx, begin == n, "SVOH_BATCH_WHOLE_SETS: the reference frames' resident sets do not add up to the batch's n");
   }
-  {
-    // the search level is chosen up to the reference pyramid's top (patch_warp.cpp:97-110) and then read
-    // from the current frame: every current frame needs at least as many levels
-    int ref_levels = 0;
-    for (int k = 0; k < n_ref_frames; ++k) ref_levels = views[k].n_levels > ref_levels ? views[k].n_levels : ref_levels;
-    for (int k = 0; k < n_cur; ++k)
-      SVOH_REQUIRE(ctx, views[n_ref_frames + k].n_levels >= ref_levels, "current frame has fewer pyramid levels than a reference frame");
+  if (whole_sets) {   // (behind the table's reuse: the remembered table is the one without the sets' beginnings)
+    const int rc = begin_whole_sets(ctx, n_ref_frames, ref_frames, views, n);
+    if (rc != SVOH_OK) return rc;
   }
-  if (!on_device)
-    for (int i = 0; i < n; ++i)
-      SVOH_REQUIRE(ctx, fb->level[i] < views[fb->ref_frame_idx[i]].n_levels, "feature level beyond the reference pyramid");
+  ctx->matcher_deferred_used[kind] = true;
+  st.valid = false;   // consumed: the outputs stay readable, a second batch needs a new svoh_matcher_stage
+  SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d, h, b.in_total));
+  MatcherArgs a = matcher_args(b, d, mopt, dopt, n, n_ref_frames, n_cur);
+  a.whole_sets = whole_sets ? 1 : 0;
+  queue_deferred(ctx, kind, a, batch_geometry(ctx, n, seeds, true, false, false, false), b, h, d, b.end, t, cur_frame[0].frame);
+  if (seeds && c.n_success) ctx->matcher_pending_counts.push_back({ c.n_success, h + b.off(kSlotSuccess), n });
+  return SVOH_OK;
+}
 
-  // Host-resident batches travel through one pinned staging block and one device block:
-  // [views | inputs | in/out | outputs]; device-resident batches stage the views only
-  // and the kernel reads and writes the caller's arrays in place.
-  Staging s;
-  const size_t o_views = wide ? s.add(wviews.data(), sizeof(DevFrameViewWide) * wviews.size()) : s.add(views.data(), sizeof(DevFrameView) * views.size());
-  size_t o_idx = 0, o_cidx = 0, o_px = 0, o_f = 0, o_grad = 0, o_level = 0, o_type = 0, o_depth = 0, o_pxcur = 0, o_lm = 0,
-         o_state = 0, o_result = 0, o_fcur = 0, o_slevel = 0, o_hinv = 0, o_A = 0, o_success = 0;
-  if (!on_device) {
-    o_idx = s.add(fb->ref_frame_idx, sizeof(int32_t) * n);
-    o_cidx = fb->cur_frame_idx ? s.add(fb->cur_frame_idx, sizeof(int32_t) * n) : 0;
-    o_px = s.add(fb->px, sizeof(double) * 2 * n);
-    o_f = s.add(fb->f, sizeof(double) * 3 * n);
-    o_grad = s.add(fb->grad, sizeof(double) * 2 * n);
-    o_level = s.add(fb->level, sizeof(int32_t) * n);
-    o_type = s.add(fb->type, (size_t)n);
-    if (seeds) o_state = s.add(state, sizeof(double) * 4 * n);
-    else { o_depth = s.add(depth, sizeof(double) * n); o_pxcur = s.add(px_cur, sizeof(double) * 2 * n); }
-    if (landmark_xyz) o_lm = s.add(landmark_xyz, sizeof(double) * 3 * n);
+// svoh_match_direct_batch[_pixelwise] / svoh_update_seeds_batch[_ex]; c: the caller's arrays besides the batch's own
+static int run_matcher(svoh_ctx* ctx, MatcherEntry entry, const svoh_matcher_options* mopt, const svoh_depth_filter_options* dopt,
+                       int n_ref_frames, const svoh_frame_view* ref_frames, const svoh_frame_view* cur_frame,
+                       const svoh_feature_batch* fb, const MatcherArrays& c)
+{
+  const bool seeds = entry == kEntryUpdateSeeds || entry == kEntryUpdateSeedsEx;
+  if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  SVOH_REQUIRE(ctx, mopt && ref_frames && cur_frame && fb && n_ref_frames >= 1, "NULL argument");
+  SVOH_REQUIRE(ctx, !c.landmark_xyz || (!seeds && !ctx->matcher_deferred), "the pixelwise warp: direct matches only, outside a deferred section");
+  const int n = fb->n;
+  if (c.n_success) *c.n_success = 0;
+  if (n <= 0) return SVOH_OK;
+  if (fb->mem_space == SVOH_MEM_STAGED) {
+    SVOH_REQUIRE(ctx, !c.landmark_xyz, "the pixelwise warp has no staged form");
+    return run_matcher_staged(ctx, seeds, mopt, dopt, n_ref_frames, ref_frames, cur_frame, fb, c);
   }
-  const size_t in_total = s.total;
-  // outputs (device only, appended)
-  auto out_add = [&](size_t bytes) { const size_t o = s.total; s.total = (s.total + bytes + 63) & ~(size_t)63; return o; };
-  if (!on_device) {
-    o_result = out_add(sizeof(int32_t) * n);
-    o_fcur = out_add(sizeof(double) * 3 * n);
-    o_slevel = out_add(sizeof(int32_t) * n);
-    o_hinv = out_add(sizeof(double) * n);
-    o_A = out_add(sizeof(double) * 4 * n);
-    o_success = out_add((size_t)n);
-    if (seeds && px_cur) o_pxcur = out_add(sizeof(double) * 2 * n);  // matcher px_cur_ of the seed update (output only)
-  }
-  const size_t o_nsucc = out_add(sizeof(int32_t));
+  const BatchRules& batch_rules = seeds ? kSeedBatchRules : kDirectBatchRules;
+  const int n_cur = (fb->cur_frame_idx && fb->n_cur_frames > 0) ? fb->n_cur_frames : 1;
+  int rc = check_feature_batch(ctx, batch_rules, kBatchForm, fb, n_ref_frames, n_cur);
+  if (rc != SVOH_OK) return rc;
+  // SVOH_BATCH_WHOLE_SETS on a DEVICE batch: the seeds' state / type / current-frame index live in the caller's device arrays in the
+  // sets' order, the columns are the reference frames' resident ones; always the packed geometry (which walks the tile-ordered copies)
+  const bool whole_sets = fb->layout == SVOH_BATCH_WHOLE_SETS;
+  const bool on_device = fb->mem_space == SVOH_MEM_DEVICE;
+  if (seeds) SVOH_REQUIRE(ctx, dopt && c.state && c.success, "NULL seed argument");
+  else SVOH_REQUIRE(ctx, c.depth && c.px_cur && c.result, "NULL match argument");
+  rc = check_feature_batch(ctx, batch_rules, kBatchRanges, fb, n_ref_frames, n_cur);
+  if (rc != SVOH_OK) return rc;
+  SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  SVOH_ALIGN_JOIN(ctx);
 
   // deferred section (svoh_matcher_begin_deferred): no synchronisation here; each deferred batch stages through
   // buffers of its own kind, which no other call touches (svoh_internal.h)
   const bool defer = ctx->matcher_deferred && !on_device;
+  std::vector<DevFrameView> views((size_t)n_ref_frames + n_cur);
+  ViewTable t;
+  const ViewRules view_rules = { "current frame", wide_views_admitted(entry, on_device, defer), false, false, whole_sets, ViewRules::kLevelsLast };
+  rc = fill_view_table(ctx, view_rules, n_ref_frames, ref_frames, n_cur, cur_frame, n, views.data(), t);
+  if (rc == SVOH_OK) rc = check_feature_batch(ctx, batch_rules, kBatchLevels, fb, n_ref_frames, n_cur, true, views.data());
+  if (rc != SVOH_OK) return rc;
+  const bool wide = !t.wide.empty();
+
+  // host arrays travel through the pinned and the device block; a device batch stages the views only, its arrays are used in place
+  MatcherBlock b;
+  if (wide) layout_matcher_batch(b, seeds, (size_t)n, t.wide.data(), sizeof(DevFrameViewWide) * t.wide.size(), *fb, c, on_device);
+  else layout_matcher_batch(b, seeds, (size_t)n, views.data(), sizeof(DevFrameView) * views.size(), *fb, c, on_device);
   if (defer) {
     SVOH_REQUIRE(ctx, !ctx->matcher_deferred_used[seeds ? 1 : 0], "one batch of each kind per deferred section: collect first");
     ctx->matcher_deferred_used[seeds ? 1 : 0] = true;
@@ -3190,156 +3421,57 @@ static int run_matcher(svoh_ctx* ctx, bool seeds, const svoh_matcher_options* mo
   PinnedBuffer& hbuf = defer ? (seeds ? ctx->h_match_seeds : ctx->h_match_direct) : ctx->h_scratch1;
   DevBuffer& dbuf = defer ? (seeds ? ctx->d_match_seeds : ctx->d_match_direct) : ctx->d_scratch1;
   if (defer && seeds) ctx->seed_block.valid = false;   // the seed block is laid out anew (svoh_align_camera::pos_seed_unit)
-  SVOH_HIP_TRY(ctx, hbuf.reserve(s.total));
-  SVOH_HIP_TRY(ctx, dbuf.reserve(s.total));
+  SVOH_HIP_TRY(ctx, hbuf.reserve(b.total));
+  SVOH_HIP_TRY(ctx, dbuf.reserve(b.total));
   uint8_t* h = static_cast<uint8_t*>(hbuf.ptr);
   uint8_t* d = static_cast<uint8_t*>(dbuf.ptr);
-  for (size_t k = 0; k < s.in.size(); ++k) memcpy(h + s.off[k], s.in[k].first, s.in[k].second);
-  SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d, h, in_total));
-  // geometry: 1 = eight lanes per unit, 0 = one lane per unit, 2 = packed (seed update only; large batches)
-  // 3 = one wave per unit (the epipolar scan 64 steps at a time; seed update only, on request: its scans are short)
-  int g8 = n <= kG8MaxUnits ? 1 : 2;
-  g8 = SvohKnobs::or_default(ctx->knobs.matcher_g8, g8);
-  if (g8 < 0 || g8 > 3) g8 = 0;
-  if (g8 == 3 && (!seeds || defer)) g8 = 1;   // the direct matcher has no scan
-  if (landmark_xyz) g8 = 0;                    // the pixelwise warp exists with one lane per unit only
-  if (whole_sets) g8 = 2;                      // (a device batch over whole sets: the packed geometry reads the resident columns itself)
-  if (wide) g8 = seeds ? 1 : 0;                // a wide launch: the twin's one geometry, whatever the size and the knob say
+  b.gather(h);
+  SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d, h, b.in_total));
+  const MatcherGeometry g = batch_geometry(ctx, n, seeds, defer, c.landmark_xyz != nullptr, whole_sets, wide);
   // Optional outputs of units that return before the matcher runs read back as zeros.  The per-unit kernels write those
   // zeros themselves (match_direct_body, update_seeds_body): a fill of the output block would be one more operation on
   // the stream of every per-frame call (2.6 us each, tools/svoh_call_overhead).  The packed geometry's kernels do not.
-  if (!on_device && g8 == 2 && !defer) SVOH_HIP_TRY(ctx, hipMemsetAsync(d + in_total, 0, s.total - in_total, ctx->stream));   // (a deferred batch: at its launch)
+  if (!on_device && g == kGeomPacked && !defer) SVOH_HIP_TRY(ctx, hipMemsetAsync(d + b.in_total, 0, b.total - b.in_total, ctx->stream));   // (a deferred batch: at its launch)
 
-  MatcherArgs a;
-  memset(&a, 0, sizeof a);
-  a.ref_frames = reinterpret_cast<const DevFrameView*>(d + o_views);
-  a.cur_frame = a.ref_frames + n_ref_frames;
-  a.mopt = *mopt;
-  if (dopt) a.dopt = *dopt;
-  a.n = n;
-  a.n_ref_frames = n_ref_frames;
-  a.n_cur_frames = n_cur;
+  MatcherArgs a = matcher_args(b, d, mopt, dopt, n, n_ref_frames, n_cur);
   a.whole_sets = whole_sets ? 1 : 0;
-  if (on_device) {
-    a.ref_frame_idx = fb->ref_frame_idx; a.cur_frame_idx = fb->cur_frame_idx;
-    a.px = fb->px; a.f = fb->f; a.grad = fb->grad; a.level = fb->level; a.type = fb->type;
-    a.result = result; a.f_cur = f_cur; a.search_level = search_level; a.h_inv = h_inv; a.A_cur_ref = A_cur_ref;
-    a.success = success; a.state = state; a.depth = depth; a.px_cur = px_cur; a.landmark_xyz = landmark_xyz;
-  } else {
-    a.ref_frame_idx = reinterpret_cast<const int32_t*>(d + o_idx);
-    a.cur_frame_idx = fb->cur_frame_idx ? reinterpret_cast<const int32_t*>(d + o_cidx) : nullptr;
-    a.px = reinterpret_cast<const double*>(d + o_px);
-    a.f = reinterpret_cast<const double*>(d + o_f);
-    a.grad = reinterpret_cast<const double*>(d + o_grad);
-    a.level = reinterpret_cast<const int32_t*>(d + o_level);
-    a.type = d + o_type;
-    a.result = reinterpret_cast<int32_t*>(d + o_result);
-    a.f_cur = reinterpret_cast<double*>(d + o_fcur);
-    a.search_level = reinterpret_cast<int32_t*>(d + o_slevel);
-    a.h_inv = reinterpret_cast<double*>(d + o_hinv);
-    a.A_cur_ref = reinterpret_cast<double*>(d + o_A);
-    a.success = d + o_success;
-    if (seeds) {
-      a.state = reinterpret_cast<double*>(d + o_state);
-      a.px_cur = px_cur ? reinterpret_cast<double*>(d + o_pxcur) : nullptr;
-    } else {
-      a.depth = reinterpret_cast<const double*>(d + o_depth);
-      a.px_cur = reinterpret_cast<double*>(d + o_pxcur);
-      a.landmark_xyz = landmark_xyz ? reinterpret_cast<const double*>(d + o_lm) : nullptr;
-    }
-  }
-  // small batches: eight lanes per unit (a launch is as slow as its slowest lane, and eight lanes get a unit done
-  // ~3x sooner); large batches: one lane per unit (fewer instructions per unit).  The knob SVOH_MATCHER_G8 (read when the context is made) forces one.
   if (defer) {
-    // Deferred section: the launch itself waits for svoh_matcher_flush / _collect, where a direct batch and a seed batch of
-    // the same per-unit geometry go out as ONE kernel (match_mixed_kernel).  Remembered: the arguments, the copy of the
-    // results back to the pinned block, and the copies from there to the caller's arrays.
-    svoh_ctx::DeferredLaunch& dl = ctx->matcher_deferred_launch[seeds ? 1 : 0];
-    dl.args.assign(reinterpret_cast<const uint8_t*>(&a), reinterpret_cast<const uint8_t*>(&a) + sizeof a);
-    dl.n = n; dl.g8 = g8; dl.valid = true; dl.seed_block_staged = false; dl.d_fidx = nullptr; dl.pose_from_results = false;
-    dl.max_w = dl.max_h = 1;
-    for (int k = 0; k < n_ref_frames; ++k) { dl.max_w = views[k].lv[0].w > dl.max_w ? views[k].lv[0].w : dl.max_w; dl.max_h = views[k].lv[0].h > dl.max_h ? views[k].lv[0].h : dl.max_h; }
-    dl.d_block = d; dl.out_off = in_total; dl.out_bytes = s.total - in_total;
-    dl.d2h_dst = h + o_type; dl.d2h_src = d + o_type; dl.d2h_bytes = o_nsucc - o_type;
-    dl.views_h = h + o_views; dl.views_d = d + o_views; dl.n_ref = n_ref_frames; dl.n_cur = n_cur;
-    dl.cur_frame_handle = cur_frame[0].frame;
-    auto later = [&](void* dst, size_t off, size_t bytes) { if (dst && bytes) ctx->matcher_pending.push_back({ dst, h + off, bytes }); };
-    if (seeds) {
-      later(fb->type, o_type, (size_t)n); later(state, o_state, sizeof(double) * 4 * n); later(success, o_success, (size_t)n);
-      later(result, o_result, sizeof(int32_t) * n); later(px_cur, o_pxcur, sizeof(double) * 2 * n);
-      later(f_cur, o_fcur, sizeof(double) * 3 * n); later(search_level, o_slevel, sizeof(int32_t) * n);
-      later(A_cur_ref, o_A, sizeof(double) * 4 * n);
-      if (n_success) ctx->matcher_pending_counts.push_back({ n_success, h + o_success, n });
-    } else {
-      later(px_cur, o_pxcur, sizeof(double) * 2 * n); later(result, o_result, sizeof(int32_t) * n);
-      later(f_cur, o_fcur, sizeof(double) * 3 * n); later(search_level, o_slevel, sizeof(int32_t) * n);
-      later(h_inv, o_hinv, sizeof(double) * n); later(A_cur_ref, o_A, sizeof(double) * 4 * n);
-    }
+    // ... and the copies from the pinned block to the caller's arrays wait for svoh_matcher_collect
+    queue_deferred(ctx, seeds ? 1 : 0, a, g, b, h, d, b.total, t, cur_frame[0].frame);
+    b.scatter(h, [&](void* dst, const void* src, size_t bytes) { ctx->matcher_pending.push_back({ dst, src, bytes }); });
+    if (seeds && c.n_success) ctx->matcher_pending_counts.push_back({ c.n_success, h + b.off(kSlotSuccess), n });
     return SVOH_OK;
   }
-  {
-    unsigned long long* dummy;
-    int rc = reset_counters(ctx, &dummy);
-    if (rc == SVOH_OK) rc = reserve_unit_counts(ctx, (size_t)n, &a.unit_counts);
-    if (rc != SVOH_OK) return rc;
-  }
-  if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_start, ctx->stream));
-  {
-    int max_w = 1, max_h = 1;
-    for (int k = 0; k < n_ref_frames; ++k) { max_w = views[k].lv[0].w > max_w ? views[k].lv[0].w : max_w; max_h = views[k].lv[0].h > max_h ? views[k].lv[0].h : max_h; }
-    const int rc = launch_matcher_kernels(ctx, seeds, g8, a, n, n_ref_frames, max_w, max_h, wide);
-    if (rc != SVOH_OK) return rc;
-  }
-  if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_stop, ctx->stream));
-  ctx->misc_timed = ctx->timing_on(); ctx->misc_launched = true;
-  {
-    int rc = reduce_unit_counts(ctx, (size_t)n);
-    if (rc != SVOH_OK) return rc;
-  }
+  rc = launch_bracket(ctx, (size_t)n, &a.unit_counts, [&] { return launch_matcher_kernels(ctx, seeds, g, a, n, n_ref_frames, t.max_w, t.max_h, wide); });
+  if (rc != SVOH_OK) return rc;
   if (on_device) {
     // results stay where the caller put them; only the success count (if asked for) comes back
-    if (seeds && n_success) {
-      int* d_ns = reinterpret_cast<int*>(d + o_nsucc);
+    if (seeds && c.n_success) {
+      int* d_ns = reinterpret_cast<int*>(d + b.off(kSlotNSuccess));
+      const int* h_ns = reinterpret_cast<const int*>(h + b.off(kSlotNSuccess));
       SVOH_HIP_TRY(ctx, hipMemsetAsync(d_ns, 0, sizeof(int), ctx->stream));
       const int blocks = (n + 255) / 256 > 256 ? 256 : (n + 255) / 256;
-      hipLaunchKernelGGL(count_success_kernel, dim3(blocks), dim3(256), 0, ctx->stream, success, n, d_ns);
+      hipLaunchKernelGGL(count_success_kernel, dim3(blocks), dim3(256), 0, ctx->stream, c.success, n, d_ns);
       SVOH_HIP_TRY(ctx, hipGetLastError());
-      SVOH_HIP_TRY(ctx, hipMemcpyAsync(h + o_nsucc, d_ns, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+      SVOH_HIP_TRY(ctx, hipMemcpyAsync(h + b.off(kSlotNSuccess), d_ns, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
       SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      *n_success = *reinterpret_cast<const int*>(h + o_nsucc);
+      *c.n_success = *h_ns;
     }
     return SVOH_OK;
   }
   // everything after the inputs that may have changed comes back in one copy
-  const size_t back_from = o_type;
-  SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, h + back_from, d + back_from, o_nsucc - back_from));
+  SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, h + b.back_from, d + b.back_from, b.end - b.back_from));
   SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  if (seeds) {
-    memcpy(fb->type, h + o_type, (size_t)n);
-    memcpy(state, h + o_state, sizeof(double) * 4 * n);
-    memcpy(success, h + o_success, (size_t)n);
-    if (result) memcpy(result, h + o_result, sizeof(int32_t) * n);
-    if (px_cur) memcpy(px_cur, h + o_pxcur, sizeof(double) * 2 * n);
-    if (f_cur) memcpy(f_cur, h + o_fcur, sizeof(double) * 3 * n);
-    if (search_level) memcpy(search_level, h + o_slevel, sizeof(int32_t) * n);
-    if (A_cur_ref) memcpy(A_cur_ref, h + o_A, sizeof(double) * 4 * n);
-    if (n_success) {
-      int c = 0;
-      for (int i = 0; i < n; ++i) c += success[i];
-      *n_success = c;
-    }
-  } else {
-    memcpy(px_cur, h + o_pxcur, sizeof(double) * 2 * n);
-    memcpy(result, h + o_result, sizeof(int32_t) * n);
-    if (f_cur) memcpy(f_cur, h + o_fcur, sizeof(double) * 3 * n);
-    if (search_level) memcpy(search_level, h + o_slevel, sizeof(int32_t) * n);
-    if (h_inv) memcpy(h_inv, h + o_hinv, sizeof(double) * n);
-    if (A_cur_ref) memcpy(A_cur_ref, h + o_A, sizeof(double) * 4 * n);
+  b.scatter(h, [](void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); });
+  if (seeds && c.n_success) {
+    int k = 0;
+    for (int i = 0; i < n; ++i) k += c.success[i];
+    *c.n_success = k;
   }
   return SVOH_OK;
 }
 
-// svoh_epipolar_match_batch: same staging scheme as run_matcher ([views | transforms | inputs | outputs])
+// svoh_epipolar_match_batch: the same scheme; it stages through the blocking batches' buffers inside a deferred section too
 static int run_epipolar(svoh_ctx* ctx, const svoh_matcher_options* mopt, int n_ref_frames, const svoh_frame_view* ref_frames,
                         const svoh_frame_view* cur_frame, const svoh_se3* T_cur_ref, const svoh_feature_batch* fb,
                         const double d_inv_common[3], const double* d_inv, const svoh_epipolar_match_outputs* out)
@@ -3349,163 +3481,65 @@ static int run_epipolar(svoh_ctx* ctx, const svoh_matcher_options* mopt, int n_r
   SVOH_REQUIRE(ctx, d_inv_common || d_inv, "no depth range given");
   const int n = fb->n;
   if (n <= 0) return SVOH_OK;
-  SVOH_REQUIRE(ctx, fb->mem_space == SVOH_MEM_HOST || fb->mem_space == SVOH_MEM_DEVICE, "bad mem_space");
-  SVOH_REQUIRE(ctx, !fb->feature_index, "feature_index: staged batches only (svoh_matcher_stage with SVOH_STAGE_RESIDENT_COLUMNS)");
-  SVOH_REQUIRE(ctx, fb->layout == SVOH_BATCH_UNITS, "svoh_feature_batch::layout: SVOH_BATCH_WHOLE_SETS is for staged seed batches over resident columns");
-  const bool on_device = fb->mem_space == SVOH_MEM_DEVICE;
-  SVOH_REQUIRE(ctx, fb->ref_frame_idx && fb->px && fb->f && fb->grad && fb->level && fb->type, "NULL feature array");
-  SVOH_REQUIRE(ctx, out->result && out->depth, "result and depth outputs are required");
   const int n_cur = (fb->cur_frame_idx && fb->n_cur_frames > 0) ? fb->n_cur_frames : 1;
-  if (!on_device) {
-    for (int i = 0; i < n; ++i) {
-      SVOH_REQUIRE(ctx, fb->ref_frame_idx[i] >= 0 && fb->ref_frame_idx[i] < n_ref_frames, "ref_frame_idx out of range");
-      SVOH_REQUIRE(ctx, fb->level[i] >= 0 && fb->level[i] < SVOH_MAX_LEVELS, "feature level out of range");
-      if (fb->cur_frame_idx)
-        SVOH_REQUIRE(ctx, fb->cur_frame_idx[i] >= 0 && fb->cur_frame_idx[i] < n_cur, "cur_frame_idx out of range");
-    }
-  }
+  int rc = check_feature_batch(ctx, kEpipolarBatchRules, kBatchForm, fb, n_ref_frames, n_cur);
+  if (rc != SVOH_OK) return rc;
+  const bool on_device = fb->mem_space == SVOH_MEM_DEVICE;
+  SVOH_REQUIRE(ctx, out->result && out->depth, "result and depth outputs are required");
+  rc = check_feature_batch(ctx, kEpipolarBatchRules, kBatchRanges, fb, n_ref_frames, n_cur);
+  if (rc != SVOH_OK) return rc;
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   SVOH_ALIGN_JOIN(ctx);
   std::vector<DevFrameView> views((size_t)n_ref_frames + n_cur);
-  int ref_levels = 0;
-  const bool wide_allowed = !on_device;   // EQUIDISTANT | ATAN views: host arrays only
-  for (int k = 0; k < n_ref_frames; ++k) {
-    const int rc = fill_view(ctx, ref_frames[k], &views[k], "reference frame", false, wide_allowed);
-    if (rc != SVOH_OK) return rc;
-    ref_levels = views[k].n_levels > ref_levels ? views[k].n_levels : ref_levels;
-  }
-  for (int k = 0; k < n_cur; ++k) {
-    const int rc = fill_view(ctx, cur_frame[k], &views[n_ref_frames + k], "current frame", false, wide_allowed);
-    if (rc != SVOH_OK) return rc;
-    SVOH_REQUIRE(ctx, views[n_ref_frames + k].n_levels >= ref_levels, "current frame has fewer pyramid levels than a reference frame");
-  }
-  std::vector<DevFrameViewWide> wviews;
-  {
-    const int rc = fill_wide_views(ctx, n_ref_frames, ref_frames, n_cur, cur_frame, wviews);
-    if (rc != SVOH_OK) return rc;
-  }
-  const bool wide = !wviews.empty();
-  if (!on_device)
-    for (int i = 0; i < n; ++i)
-      SVOH_REQUIRE(ctx, fb->level[i] < views[fb->ref_frame_idx[i]].n_levels, "feature level beyond the reference pyramid");
+  ViewTable t;
+  const ViewRules view_rules = { "current frame", wide_views_admitted(kEntryEpipolar, on_device, false), false, false, false, ViewRules::kLevelsByFrame };
+  rc = fill_view_table(ctx, view_rules, n_ref_frames, ref_frames, n_cur, cur_frame, n, views.data(), t);
+  if (rc == SVOH_OK) rc = check_feature_batch(ctx, kEpipolarBatchRules, kBatchLevels, fb, n_ref_frames, n_cur, true, views.data());
+  if (rc != SVOH_OK) return rc;
+  const bool wide = !t.wide.empty();
   std::vector<Rigid> T;
   if (T_cur_ref) {
     T.resize((size_t)n_ref_frames * n_cur);
     for (size_t k = 0; k < T.size(); ++k) T[k] = load_rigid(T_cur_ref[k]);
   }
 
-  Staging s;
-  const size_t o_views = wide ? s.add(wviews.data(), sizeof(DevFrameViewWide) * wviews.size()) : s.add(views.data(), sizeof(DevFrameView) * views.size());
-  const size_t o_T = T_cur_ref ? s.add(T.data(), sizeof(Rigid) * T.size()) : 0;
-  size_t o_idx = 0, o_cidx = 0, o_px = 0, o_f = 0, o_grad = 0, o_level = 0, o_type = 0, o_dinv = 0;
-  if (!on_device) {
-    o_idx = s.add(fb->ref_frame_idx, sizeof(int32_t) * n);
-    o_cidx = fb->cur_frame_idx ? s.add(fb->cur_frame_idx, sizeof(int32_t) * n) : 0;
-    o_px = s.add(fb->px, sizeof(double) * 2 * n);
-    o_f = s.add(fb->f, sizeof(double) * 3 * n);
-    o_grad = s.add(fb->grad, sizeof(double) * 2 * n);
-    o_level = s.add(fb->level, sizeof(int32_t) * n);
-    o_type = s.add(fb->type, (size_t)n);
-    o_dinv = d_inv ? s.add(d_inv, sizeof(double) * 3 * n) : 0;
-  }
-  const size_t in_total = s.total;
-  auto out_add = [&](size_t bytes) { const size_t o = s.total; s.total = (s.total + bytes + 63) & ~(size_t)63; return o; };
-  size_t o_result = 0, o_depth = 0, o_pxcur = 0, o_fcur = 0, o_slevel = 0, o_hinv = 0, o_A = 0;
-  if (!on_device) {
-    o_result = out_add(sizeof(int32_t) * n);
-    o_depth = out_add(sizeof(double) * n);
-    o_pxcur = out_add(sizeof(double) * 2 * n);
-    o_fcur = out_add(sizeof(double) * 3 * n);
-    o_slevel = out_add(sizeof(int32_t) * n);
-    o_hinv = out_add(sizeof(double) * n);
-    o_A = out_add(sizeof(double) * 4 * n);
-  }
-  const size_t o_end = s.total;
-  SVOH_HIP_TRY(ctx, ctx->h_scratch1.reserve(s.total));
-  SVOH_HIP_TRY(ctx, ctx->d_scratch1.reserve(s.total));
+  MatcherArrays c;
+  c.d_inv = d_inv;
+  c.result = out->result; c.depth_out = out->depth; c.px_cur = out->px_cur; c.f_cur = out->f_cur;
+  c.search_level = out->search_level; c.h_inv = out->h_inv; c.A_cur_ref = out->A_cur_ref;
+  MatcherBlock b;
+  const void* const T_host = T_cur_ref ? T.data() : nullptr;
+  if (wide) layout_epipolar_batch(b, (size_t)n, t.wide.data(), sizeof(DevFrameViewWide) * t.wide.size(), T_host, sizeof(Rigid) * T.size(), *fb, c, on_device);
+  else layout_epipolar_batch(b, (size_t)n, views.data(), sizeof(DevFrameView) * views.size(), T_host, sizeof(Rigid) * T.size(), *fb, c, on_device);
+  SVOH_HIP_TRY(ctx, ctx->h_scratch1.reserve(b.total));
+  SVOH_HIP_TRY(ctx, ctx->d_scratch1.reserve(b.total));
   uint8_t* h = static_cast<uint8_t*>(ctx->h_scratch1.ptr);
   uint8_t* d = static_cast<uint8_t*>(ctx->d_scratch1.ptr);
-  for (size_t k = 0; k < s.in.size(); ++k) memcpy(h + s.off[k], s.in[k].first, s.in[k].second);
-  SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d, h, in_total));
-  if (!on_device && o_end > in_total) SVOH_HIP_TRY(ctx, hipMemsetAsync(d + in_total, 0, o_end - in_total, ctx->stream));
+  b.gather(h);
+  SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d, h, b.in_total));
+  if (!on_device && b.end > b.in_total) SVOH_HIP_TRY(ctx, hipMemsetAsync(d + b.in_total, 0, b.end - b.in_total, ctx->stream));
 
-  MatcherArgs a;
-  memset(&a, 0, sizeof a);
-  a.ref_frames = reinterpret_cast<const DevFrameView*>(d + o_views);
-  a.cur_frame = a.ref_frames + n_ref_frames;
-  a.T_cur_ref = T_cur_ref ? reinterpret_cast<const Rigid*>(d + o_T) : nullptr;
-  a.mopt = *mopt;
-  a.n = n;
-  a.n_ref_frames = n_ref_frames;
-  a.n_cur_frames = n_cur;
+  MatcherArgs a = matcher_args(b, d, mopt, nullptr, n, n_ref_frames, n_cur);
   if (d_inv_common) for (int k = 0; k < 3; ++k) a.d_inv_common[k] = d_inv_common[k];
-  if (on_device) {
-    a.ref_frame_idx = fb->ref_frame_idx; a.cur_frame_idx = fb->cur_frame_idx;
-    a.px = fb->px; a.f = fb->f; a.grad = fb->grad; a.level = fb->level; a.type = fb->type;
-    a.d_inv = d_inv;
-    a.result = out->result; a.depth_out = out->depth; a.px_cur = out->px_cur; a.f_cur = out->f_cur;
-    a.search_level = out->search_level; a.h_inv = out->h_inv; a.A_cur_ref = out->A_cur_ref;
-  } else {
-    a.ref_frame_idx = reinterpret_cast<const int32_t*>(d + o_idx);
-    a.cur_frame_idx = fb->cur_frame_idx ? reinterpret_cast<const int32_t*>(d + o_cidx) : nullptr;
-    a.px = reinterpret_cast<const double*>(d + o_px);
-    a.f = reinterpret_cast<const double*>(d + o_f);
-    a.grad = reinterpret_cast<const double*>(d + o_grad);
-    a.level = reinterpret_cast<const int32_t*>(d + o_level);
-    a.type = d + o_type;
-    a.d_inv = d_inv ? reinterpret_cast<const double*>(d + o_dinv) : nullptr;
-    a.result = reinterpret_cast<int32_t*>(d + o_result);
-    a.depth_out = reinterpret_cast<double*>(d + o_depth);
-    a.px_cur = reinterpret_cast<double*>(d + o_pxcur);
-    a.f_cur = reinterpret_cast<double*>(d + o_fcur);
-    a.search_level = reinterpret_cast<int32_t*>(d + o_slevel);
-    a.h_inv = reinterpret_cast<double*>(d + o_hinv);
-    a.A_cur_ref = reinterpret_cast<double*>(d + o_A);
-  }
-  // geometry as in run_matcher: 1 = eight lanes per unit, 0 = one lane per unit, 2 = packed (large batches),
-  // 3 = one wave per unit, the scan 64 steps at a time: what a long search (the stereo seam's 500 steps) gets while the
-  // batch leaves the device room for a wave per feature (a launch is as slow as its slowest feature: 8 rounds instead of 63)
-  constexpr int kW64MaxUnits = 16384;
-  int g8 = n <= kG8MaxUnits ? ((mopt->max_epi_search_steps > 128 && n <= kW64MaxUnits) ? 3 : 1) : 2;
-  g8 = SvohKnobs::or_default(ctx->knobs.matcher_g8, g8);
-  if (g8 < 0 || g8 > 3) g8 = 0;
-  if (wide) g8 = 3;   // a wide launch: the twin's one geometry (one wave per unit), whatever the size and the knob say
-  const int units_per_block = g8 == 1 ? 8 : (g8 == 3 ? 1 : 64);
-  const dim3 grid((unsigned)((n + units_per_block - 1) / units_per_block)), block(64);
-  {
-    unsigned long long* dummy;
-    int rc = reset_counters(ctx, &dummy);
-    if (rc == SVOH_OK) rc = reserve_unit_counts(ctx, (size_t)n, &a.unit_counts);
-    if (rc != SVOH_OK) return rc;
-  }
-  if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_start, ctx->stream));
-  if (wide) hipLaunchKernelGGL(epipolar_match_wide_kernel<3>, grid, block, 0, ctx->stream, widen_args(a));
-  else if (g8 == 2) hipLaunchKernelGGL(match_packed_kernel<false>, dim3((unsigned)((n + kPkThreads - 1) / kPkThreads)), dim3(kPkThreads), 0, ctx->stream, a);
-  else if (g8 == 3) hipLaunchKernelGGL(epipolar_match_kernel<3>, grid, block, 0, ctx->stream, a);
-  else if (g8) hipLaunchKernelGGL(epipolar_match_kernel<1>, grid, block, 0, ctx->stream, a);
-  else hipLaunchKernelGGL(epipolar_match_kernel<0>, grid, block, 0, ctx->stream, a);
-  SVOH_HIP_TRY(ctx, hipGetLastError());
-  if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_stop, ctx->stream));
-  ctx->misc_timed = ctx->timing_on(); ctx->misc_launched = true;
-  {
-    const int rc = reduce_unit_counts(ctx, (size_t)n);
-    if (rc != SVOH_OK) return rc;
-  }
-  if (on_device) return SVOH_OK;
-  SVOH_HIP_TRY(ctx, hipMemcpyAsync(h + o_result, d + o_result, o_end - o_result, hipMemcpyDeviceToHost, ctx->stream));
+  const MatcherGeometry g = epipolar_geometry(ctx, n, mopt->max_epi_search_steps, wide);
+  const dim3 grid((unsigned)((n + units_per_block(g) - 1) / units_per_block(g))), block(64);
+  rc = launch_bracket(ctx, (size_t)n, &a.unit_counts, [&] {
+    if (wide) hipLaunchKernelGGL(epipolar_match_wide_kernel<3>, grid, block, 0, ctx->stream, widen_args(a));
+    else if (g == kGeomPacked) hipLaunchKernelGGL(match_packed_kernel<false>, dim3((unsigned)((n + kPkThreads - 1) / kPkThreads)), dim3(kPkThreads), 0, ctx->stream, a);
+    else if (g == kGeomOneWave) hipLaunchKernelGGL(epipolar_match_kernel<3>, grid, block, 0, ctx->stream, a);
+    else if (g == kGeomEightLanes) hipLaunchKernelGGL(epipolar_match_kernel<1>, grid, block, 0, ctx->stream, a);
+    else hipLaunchKernelGGL(epipolar_match_kernel<0>, grid, block, 0, ctx->stream, a);
+    return (int)SVOH_OK;
+  });
+  if (rc != SVOH_OK || on_device) return rc;
+  SVOH_HIP_TRY(ctx, hipMemcpyAsync(h + b.back_from, d + b.back_from, b.end - b.back_from, hipMemcpyDeviceToHost, ctx->stream));
   SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(out->result, h + o_result, sizeof(int32_t) * n);
-  memcpy(out->depth, h + o_depth, sizeof(double) * n);
-  if (out->px_cur) memcpy(out->px_cur, h + o_pxcur, sizeof(double) * 2 * n);
-  if (out->f_cur) memcpy(out->f_cur, h + o_fcur, sizeof(double) * 3 * n);
-  if (out->search_level) memcpy(out->search_level, h + o_slevel, sizeof(int32_t) * n);
-  if (out->h_inv) memcpy(out->h_inv, h + o_hinv, sizeof(double) * n);
-  if (out->A_cur_ref) memcpy(out->A_cur_ref, h + o_A, sizeof(double) * 4 * n);
+  b.scatter(h, [](void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); });
   return SVOH_OK;
 }
 
-// svoh_update_seeds_chain: [views (reference, then chain frames) | chains | inputs | state, type | outputs] through a staging
-// pair of its own (h_seed_chain / d_seed_chain): the deferred section's queued or flushed batches are not touched
+// svoh_update_seeds_chain, through a staging pair of its own (h_seed_chain / d_seed_chain): the deferred section's queued or
+// flushed batches are not touched
 static int run_seed_chain(svoh_ctx* ctx, const svoh_matcher_options* mopt, const svoh_depth_filter_options* dopt, int n_ref_frames,
                           const svoh_frame_view* ref_frames, const svoh_feature_batch* fb, double* state, int n_chain_frames,
                           const svoh_frame_view* chain_frames, const int32_t* chain_begin, const int32_t* chain_idx,
@@ -3517,10 +3551,8 @@ static int run_seed_chain(svoh_ctx* ctx, const svoh_matcher_options* mopt, const
   if (n_success) *n_success = 0;
   if (n <= 0) return SVOH_OK;
   SVOH_REQUIRE(ctx, ref_frames && chain_begin && n_ref_frames >= 1 && n_chain_frames >= 0, "NULL argument");
-  SVOH_REQUIRE(ctx, fb->mem_space == SVOH_MEM_HOST, "svoh_update_seeds_chain: host arrays only (SVOH_MEM_HOST)");
-  SVOH_REQUIRE(ctx, fb->layout == SVOH_BATCH_UNITS && !fb->feature_index && !fb->cur_frame_idx,
-               "svoh_update_seeds_chain: SVOH_BATCH_UNITS without feature_index and cur_frame_idx (the chains name the current frames)");
-  SVOH_REQUIRE(ctx, fb->ref_frame_idx && fb->px && fb->f && fb->grad && fb->level && fb->type && state && steps_succeeded, "NULL feature array");
+  int rc = check_feature_batch(ctx, kChainBatchRules, kBatchForm, fb, n_ref_frames, n_chain_frames, state && steps_succeeded);
+  if (rc != SVOH_OK) return rc;
   const bool want_steps = step_result || step_success;
   SVOH_REQUIRE(ctx, !want_steps || max_steps >= 0, "max_steps is negative");
   // the chains
@@ -3535,25 +3567,19 @@ static int run_seed_chain(svoh_ctx* ctx, const svoh_matcher_options* mopt, const
   for (int k = 0; k < n_links; ++k)
     SVOH_REQUIRE(ctx, chain_idx[k] >= 0 && chain_idx[k] < n_chain_frames, "chain_idx out of range");
   SVOH_REQUIRE(ctx, !want_steps || max_steps >= longest, "max_steps is smaller than the longest chain");
-  for (int i = 0; i < n; ++i) {
-    SVOH_REQUIRE(ctx, fb->ref_frame_idx[i] >= 0 && fb->ref_frame_idx[i] < n_ref_frames, "ref_frame_idx out of range");
-    SVOH_REQUIRE(ctx, fb->level[i] >= 0 && fb->level[i] < SVOH_MAX_LEVELS, "feature level out of range");
-  }
+  rc = check_feature_batch(ctx, kChainBatchRules, kBatchRanges, fb, n_ref_frames, n_chain_frames);
+  if (rc != SVOH_OK) return rc;
   std::vector<DevFrameView> views((size_t)n_ref_frames + n_chain_frames);
-  for (int k = 0; k < n_ref_frames; ++k) {
-    const int rc = fill_view(ctx, ref_frames[k], &views[k], "reference frame");
-    if (rc != SVOH_OK) return rc;
-  }
-  for (int k = 0; k < n_chain_frames; ++k) {
-    const int rc = fill_view(ctx, chain_frames[k], &views[n_ref_frames + k], "chain frame");
-    if (rc != SVOH_OK) return rc;
-  }
-  // the search level is chosen up to the reference pyramid's top and read from the current frame (run_matcher)
+  ViewTable t;
+  const ViewRules view_rules = { "chain frame", wide_views_admitted(kEntrySeedChain, false, false), false, false, false, ViewRules::kLevelsNotHere };
+  rc = fill_view_table(ctx, view_rules, n_ref_frames, ref_frames, n_chain_frames, chain_frames, n, views.data(), t);
+  if (rc != SVOH_OK) return rc;
+  // the search level is chosen up to the reference pyramid's top and read from the current frame (ViewRules)
   for (int r = 0; r < n_ref_frames; ++r)
     for (int k = chain_begin[r]; k < chain_begin[r + 1]; ++k)
       SVOH_REQUIRE(ctx, views[n_ref_frames + chain_idx[k]].n_levels >= views[r].n_levels, "a chain frame has fewer pyramid levels than its reference frame");
-  for (int i = 0; i < n; ++i)
-    SVOH_REQUIRE(ctx, fb->level[i] < views[fb->ref_frame_idx[i]].n_levels, "feature level beyond the reference pyramid");
+  rc = check_feature_batch(ctx, kChainBatchRules, kBatchLevels, fb, n_ref_frames, n_chain_frames, true, views.data());
+  if (rc != SVOH_OK) return rc;
   const size_t n_steps_out = want_steps ? (size_t)n * max_steps : 0;
   if (n_links == 0) {   // nothing to walk: no launch
     memset(steps_succeeded, 0, sizeof(int32_t) * n);
@@ -3564,84 +3590,32 @@ static int run_seed_chain(svoh_ctx* ctx, const svoh_matcher_options* mopt, const
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   SVOH_ALIGN_JOIN(ctx);
 
-  Staging s;
-  const size_t o_views = s.add(views.data(), sizeof(DevFrameView) * views.size());
-  const size_t o_begin = s.add(chain_begin, sizeof(int32_t) * ((size_t)n_ref_frames + 1));
-  const size_t o_cidx = s.add(chain_idx, sizeof(int32_t) * n_links);
-  const size_t o_idx = s.add(fb->ref_frame_idx, sizeof(int32_t) * n);
-  const size_t o_px = s.add(fb->px, sizeof(double) * 2 * n);
-  const size_t o_f = s.add(fb->f, sizeof(double) * 3 * n);
-  const size_t o_grad = s.add(fb->grad, sizeof(double) * 2 * n);
-  const size_t o_level = s.add(fb->level, sizeof(int32_t) * n);
-  const size_t o_type = s.add(fb->type, (size_t)n);
-  const size_t o_state = s.add(state, sizeof(double) * 4 * n);
-  const size_t in_total = s.total;
-  auto out_add = [&](size_t bytes) { const size_t o = s.total; s.total = (s.total + bytes + 63) & ~(size_t)63; return o; };
-  const size_t o_nok = out_add(sizeof(int32_t) * n);
-  const size_t o_sres = step_result ? out_add(sizeof(int32_t) * n_steps_out) : 0;
-  const size_t o_ssucc = step_success ? out_add(n_steps_out) : 0;
-  const size_t o_end = s.total;
-  SVOH_HIP_TRY(ctx, ctx->h_seed_chain.reserve(s.total));
-  SVOH_HIP_TRY(ctx, ctx->d_seed_chain.reserve(s.total));
+  MatcherBlock b;
+  layout_seed_chain(b, (size_t)n, views.data(), sizeof(DevFrameView) * views.size(), (size_t)n_ref_frames, chain_begin, (size_t)n_links, chain_idx,
+                    *fb, state, steps_succeeded, step_result, step_success, n_steps_out);
+  SVOH_HIP_TRY(ctx, ctx->h_seed_chain.reserve(b.total));
+  SVOH_HIP_TRY(ctx, ctx->d_seed_chain.reserve(b.total));
   uint8_t* h = static_cast<uint8_t*>(ctx->h_seed_chain.ptr);
   uint8_t* d = static_cast<uint8_t*>(ctx->d_seed_chain.ptr);
-  for (size_t k = 0; k < s.in.size(); ++k) memcpy(h + s.off[k], s.in[k].first, s.in[k].second);
-  SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d, h, in_total));
+  b.gather(h);
+  SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d, h, b.in_total));
 
-  MatcherArgs a;
-  memset(&a, 0, sizeof a);
-  a.ref_frames = reinterpret_cast<const DevFrameView*>(d + o_views);
-  a.cur_frame = a.ref_frames + n_ref_frames;
-  a.mopt = *mopt;
-  a.dopt = *dopt;
-  a.n = n;
-  a.n_ref_frames = n_ref_frames;
-  a.n_cur_frames = n_chain_frames;
-  a.ref_frame_idx = reinterpret_cast<const int32_t*>(d + o_idx);
-  a.px = reinterpret_cast<const double*>(d + o_px);
-  a.f = reinterpret_cast<const double*>(d + o_f);
-  a.grad = reinterpret_cast<const double*>(d + o_grad);
-  a.level = reinterpret_cast<const int32_t*>(d + o_level);
-  a.type = d + o_type;
-  a.state = reinterpret_cast<double*>(d + o_state);
   SeedChainArgs c;
-  c.chain_begin = reinterpret_cast<const int32_t*>(d + o_begin);
-  c.chain_idx = reinterpret_cast<const int32_t*>(d + o_cidx);
-  c.steps_succeeded = reinterpret_cast<int32_t*>(d + o_nok);
-  c.step_result = step_result ? reinterpret_cast<int32_t*>(d + o_sres) : nullptr;
-  c.step_success = step_success ? d + o_ssucc : nullptr;
+  MatcherArgs a = matcher_args(b, d, mopt, dopt, n, n_ref_frames, n_chain_frames, &c);
   c.max_steps = want_steps ? max_steps : 0;
-  // the geometries of a small seed batch: eight lanes per unit unless the knob asks for one lane (0) or one wave (3);
-  // there is no packed form (2: eight lanes)
-  int g8 = SvohKnobs::or_default(ctx->knobs.matcher_g8, 1);
-  if (g8 != 0 && g8 != 3) g8 = 1;
-  const int units_per_block = g8 == 1 ? 8 : (g8 == 3 ? 1 : 64);
-  const dim3 grid((unsigned)((n + units_per_block - 1) / units_per_block)), block(64);
-  {
-    unsigned long long* dummy;
-    int rc = reset_counters(ctx, &dummy);
-    if (rc == SVOH_OK) rc = reserve_unit_counts(ctx, (size_t)n, &a.unit_counts);
-    if (rc != SVOH_OK) return rc;
-  }
-  if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_start, ctx->stream));
-  if (g8 == 3) hipLaunchKernelGGL(update_seeds_chain_kernel<3>, grid, block, 0, ctx->stream, a, c);
-  else if (g8) hipLaunchKernelGGL(update_seeds_chain_kernel<1>, grid, block, 0, ctx->stream, a, c);
-  else hipLaunchKernelGGL(update_seeds_chain_kernel<0>, grid, block, 0, ctx->stream, a, c);
-  SVOH_HIP_TRY(ctx, hipGetLastError());
-  if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_stop, ctx->stream));
-  ctx->misc_timed = ctx->timing_on(); ctx->misc_launched = true;
-  {
-    const int rc = reduce_unit_counts(ctx, (size_t)n);
-    if (rc != SVOH_OK) return rc;
-  }
+  const MatcherGeometry g = chain_geometry(ctx);
+  const dim3 grid((unsigned)((n + units_per_block(g) - 1) / units_per_block(g))), block(64);
+  rc = launch_bracket(ctx, (size_t)n, &a.unit_counts, [&] {
+    if (g == kGeomOneWave) hipLaunchKernelGGL(update_seeds_chain_kernel<3>, grid, block, 0, ctx->stream, a, c);
+    else if (g == kGeomEightLanes) hipLaunchKernelGGL(update_seeds_chain_kernel<1>, grid, block, 0, ctx->stream, a, c);
+    else hipLaunchKernelGGL(update_seeds_chain_kernel<0>, grid, block, 0, ctx->stream, a, c);
+    return (int)SVOH_OK;
+  });
+  if (rc != SVOH_OK) return rc;
   // type, state and the outputs lie behind one another: one copy back
-  SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, h + o_type, d + o_type, o_end - o_type));
+  SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, h + b.back_from, d + b.back_from, b.end - b.back_from));
   SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(fb->type, h + o_type, (size_t)n);
-  memcpy(state, h + o_state, sizeof(double) * 4 * n);
-  memcpy(steps_succeeded, h + o_nok, sizeof(int32_t) * n);
-  if (step_result) memcpy(step_result, h + o_sres, sizeof(int32_t) * n_steps_out);
-  if (step_success && n_steps_out) memcpy(step_success, h + o_ssucc, n_steps_out);
+  b.scatter(h, [](void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); });
   if (n_success) {
     int32_t total = 0;
     for (int i = 0; i < n; ++i) total += steps_succeeded[i];
@@ -3649,6 +3623,7 @@ static int run_seed_chain(svoh_ctx* ctx, const svoh_matcher_options* mopt, const
   }
   return SVOH_OK;
 }
+
 
 
 // ---- f-4: candidate projection of Reprojector::reprojectFrames ---------------------------------------------------
@@ -3778,180 +3753,6 @@ static int enqueue_candidates(svoh_ctx* ctx, const svoh_camera* cam, const svoh_
 }
 
 
-// ---- a matcher batch staged in place (svoh_matcher_stage, SVOH_MEM_STAGED) -------------------------------------------
-// The caller -- the lock-step front end of many camera streams, with one host thread per few streams -- writes a batch's
-// inputs straight into the section's page-locked block and reads its outputs from there: no concatenation of per-stream
-// arrays, no staging copy inside the call, no copy to caller arrays at collect (at 32 streams those were 3 - 5 MB each way
-// per batch, on ONE thread).  Layout: [views (max) | ref idx | cur idx | px | f | grad | level | (direct: depth) |
-// type | (direct: px_cur in/out; seeds: state in/out) | result | success | (match outputs) | n_success]; everything from
-// `type` on comes back.
-static void layout_matcher_stage(bool seeds, int n, int max_views, bool want_outputs, bool resident, svoh_ctx::MatcherStage* st)
-{
-  size_t total = 0;
-  auto add = [&](size_t bytes) { const size_t o = total; total = (total + bytes + 63) & ~(size_t)63; return o; };
-  const size_t nn = (size_t)n;
-  st->n = n; st->max_views = max_views; st->want_outputs = want_outputs || !seeds; st->resident = resident;
-  st->o_views = add(sizeof(DevFrameView) * (size_t)max_views);
-  st->o_idx = add(4 * nn); st->o_cidx = add(4 * nn);
-  // features named by index: the four columns exist on the device only (behind everything that crosses PCIe, see below)
-  st->o_fidx = resident ? add(4 * nn) : 0;
-  if (!resident) { st->o_px = add(16 * nn); st->o_f = add(24 * nn); st->o_grad = add(16 * nn); st->o_level = add(4 * nn); }
-  st->o_depth = seeds ? 0 : add(8 * nn);
-  st->o_type = add(nn);
-  st->back_from = st->o_type;
-  if (seeds) { st->o_state = add(32 * nn); st->o_pxcur = 0; }
-  else { st->o_pxcur = add(16 * nn); st->o_state = 0; }
-  st->in_total = total;
-  st->o_result = add(4 * nn); st->o_success = add(nn);
-  if (st->want_outputs) {
-    if (seeds) st->o_pxcur = add(16 * nn);
-    st->o_fcur = add(24 * nn); st->o_slevel = add(4 * nn); st->o_hinv = add(8 * nn); st->o_A = add(32 * nn);
-  } else {
-    st->o_fcur = st->o_slevel = st->o_hinv = st->o_A = 0;
-  }
-  st->o_nsucc = add(sizeof(int32_t));
-  if (resident) { st->o_px = add(16 * nn); st->o_f = add(24 * nn); st->o_grad = add(16 * nn); st->o_level = add(4 * nn); }
-  st->total = total;
-}
-
-static int run_matcher_staged(svoh_ctx* ctx, bool seeds, const svoh_matcher_options* mopt, const svoh_depth_filter_options* dopt,
-                              int n_ref_frames, const svoh_frame_view* ref_frames, const svoh_frame_view* cur_frame,
-                              const svoh_feature_batch* fb, const double* depth, double* px_cur, int32_t* result, double* f_cur,
-                              int32_t* search_level, double* h_inv, double* A_cur_ref, double* state, uint8_t* success, int32_t* n_success)
-{
-  const int kind = seeds ? 1 : 0;
-  svoh_ctx::MatcherStage& st = ctx->matcher_stage[kind];
-  SVOH_REQUIRE(ctx, ctx->matcher_deferred, "a staged batch lives in a deferred section (svoh_matcher_begin_deferred)");
-  SVOH_REQUIRE(ctx, st.valid, "no staged block of this kind: svoh_matcher_stage first");
-  SVOH_REQUIRE(ctx, !ctx->matcher_deferred_used[kind], "one batch of each kind per deferred section: collect first");
-  const int n = fb->n;
-  PinnedBuffer& hbuf = seeds ? ctx->h_match_seeds : ctx->h_match_direct;
-  DevBuffer& dbuf = seeds ? ctx->d_match_seeds : ctx->d_match_direct;
-  uint8_t* h = static_cast<uint8_t*>(hbuf.ptr);
-  uint8_t* d = static_cast<uint8_t*>(dbuf.ptr);
-  SVOH_REQUIRE(ctx, n == st.n && h && d && hbuf.cap >= st.total && dbuf.cap >= st.total, "not the batch that was staged (n differs)");
-  const int n_cur = fb->n_cur_frames > 0 ? fb->n_cur_frames : 1;
-  SVOH_REQUIRE(ctx, n_ref_frames + n_cur <= st.max_views, "more frames than the staged block has room for (max_frame_views)");
-  // the arrays must be the staged ones: anything else would silently be ignored
-  auto at = [&](size_t off) { return static_cast<void*>(h + off); };
-  SVOH_REQUIRE(ctx, fb->ref_frame_idx == at(st.o_idx) && fb->cur_frame_idx == at(st.o_cidx) && fb->type == at(st.o_type),
-               "a staged batch's feature arrays must be the pointers svoh_matcher_stage handed out");
-  const bool whole_sets = fb->layout == SVOH_BATCH_WHOLE_SETS;
-  SVOH_REQUIRE(ctx, fb->layout == SVOH_BATCH_UNITS || whole_sets, "svoh_feature_batch::layout: SVOH_BATCH_UNITS or SVOH_BATCH_WHOLE_SETS");
-  SVOH_REQUIRE(ctx, !whole_sets || (seeds && st.resident), "SVOH_BATCH_WHOLE_SETS: seed batches staged with SVOH_STAGE_RESIDENT_COLUMNS");
-  if (st.resident)
-    SVOH_REQUIRE(ctx, fb->feature_index == at(st.o_fidx) && !fb->px && !fb->f && !fb->grad && !fb->level,
-                 "a batch staged with SVOH_STAGE_RESIDENT_COLUMNS names its features by feature_index (the staged pointer); px / f / grad / level are NULL");
-  else
-    SVOH_REQUIRE(ctx, !fb->feature_index && fb->px == at(st.o_px) && fb->f == at(st.o_f) && fb->grad == at(st.o_grad) && fb->level == at(st.o_level),
-                 "a staged batch's feature arrays must be the pointers svoh_matcher_stage handed out");
-  if (seeds) {
-    SVOH_REQUIRE(ctx, dopt && state == at(st.o_state) && success == at(st.o_success), "a staged seed batch's state / success must be the staged pointers");
-    SVOH_REQUIRE(ctx, !result || result == at(st.o_result), "result: not the staged pointer");
-    SVOH_REQUIRE(ctx, st.want_outputs || (!px_cur && !f_cur && !search_level && !A_cur_ref), "the block was staged without match outputs");
-    if (st.want_outputs)
-      SVOH_REQUIRE(ctx, (!px_cur || px_cur == at(st.o_pxcur)) && (!f_cur || f_cur == at(st.o_fcur)) && (!search_level || search_level == at(st.o_slevel)) &&
-                            (!A_cur_ref || A_cur_ref == at(st.o_A)), "match outputs: not the staged pointers");
-  } else {
-    SVOH_REQUIRE(ctx, depth == at(st.o_depth) && px_cur == at(st.o_pxcur) && result == at(st.o_result), "a staged direct batch's depth / px_cur / result must be the staged pointers");
-    SVOH_REQUIRE(ctx, (!f_cur || f_cur == at(st.o_fcur)) && (!search_level || search_level == at(st.o_slevel)) && (!h_inv || h_inv == at(st.o_hinv)) &&
-                          (!A_cur_ref || A_cur_ref == at(st.o_A)), "match outputs: not the staged pointers");
-  }
-  SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  SVOH_ALIGN_JOIN(ctx);
-  DevFrameView* views = reinterpret_cast<DevFrameView*>(h + st.o_views);
-  int ref_levels = 0, max_w = 1, max_h = 1;
-  bool pose_from_results = false;
-  // the same frames as the last staged batch asked for, none released since: that batch's table (a reprojection's direct and
-  // seed batch name the same keyframes and current frames; a table of 60 views is 10 us of look-ups on the caller's thread)
-  const size_t key_bytes = sizeof(svoh_frame_view) * (size_t)(n_ref_frames + n_cur);
-  bool reuse = ctx->staged_views_generation == ctx->handle_generation && ctx->staged_views_key.size() == key_bytes + sizeof(int) &&
-               memcmp(ctx->staged_views_key.data(), &n_ref_frames, sizeof(int)) == 0 &&
-               memcmp(ctx->staged_views_key.data() + sizeof(int), ref_frames, sizeof(svoh_frame_view) * (size_t)n_ref_frames) == 0 &&
-               memcmp(ctx->staged_views_key.data() + sizeof(int) + sizeof(svoh_frame_view) * (size_t)n_ref_frames, cur_frame, sizeof(svoh_frame_view) * (size_t)n_cur) == 0;
-  for (int k = 0; k < n_cur && reuse; ++k) reuse = cur_frame[k].pose_result_index_plus1 == 0;   // (those go through the checks below)
-  if (reuse) {
-    memcpy(views, ctx->staged_views_resolved.data(), sizeof(DevFrameView) * (size_t)(n_ref_frames + n_cur));
-    ref_levels = ctx->staged_views_ref_levels; max_w = ctx->staged_views_max_w; max_h = ctx->staged_views_max_h;
-    if (st.resident) for (int k = 0; k < n_ref_frames; ++k) SVOH_REQUIRE(ctx, ref_frames[k].features != 0, "a reference frame of a batch with feature_index has no resident columns (svoh_frame_view::features)");
-  } else {
-    for (int k = 0; k < n_ref_frames; ++k) {
-      const int rc = fill_view(ctx, ref_frames[k], &views[k], "reference frame");
-      if (rc != SVOH_OK) return rc;
-      ref_levels = views[k].n_levels > ref_levels ? views[k].n_levels : ref_levels;
-      max_w = views[k].lv[0].w > max_w ? views[k].lv[0].w : max_w; max_h = views[k].lv[0].h > max_h ? views[k].lv[0].h : max_h;
-      SVOH_REQUIRE(ctx, !st.resident || ref_frames[k].features != 0, "a reference frame of a batch with feature_index has no resident columns (svoh_frame_view::features)");
-    }
-    for (int k = 0; k < n_cur; ++k) {
-      const int rc = fill_view(ctx, cur_frame[k], &views[n_ref_frames + k], "current frame", seeds && ctx->in_pose_hook);
-      if (rc != SVOH_OK) return rc;
-      SVOH_REQUIRE(ctx, views[n_ref_frames + k].n_levels >= ref_levels, "current frame has fewer pyramid levels than a reference frame");
-      const int pr = views[n_ref_frames + k].pose_result_index_plus1;
-      SVOH_REQUIRE(ctx, pr >= 0 && pr <= ctx->n_pose_results, "pose_result_index_plus1: the pose batch in flight has no such result");
-      pose_from_results = pose_from_results || pr > 0;
-    }
-    ctx->staged_views_generation = ~0ull;
-    if (!pose_from_results) {
-      ctx->staged_views_key.resize(key_bytes + sizeof(int));
-      memcpy(ctx->staged_views_key.data(), &n_ref_frames, sizeof(int));
-      memcpy(ctx->staged_views_key.data() + sizeof(int), ref_frames, sizeof(svoh_frame_view) * (size_t)n_ref_frames);
-      memcpy(ctx->staged_views_key.data() + sizeof(int) + sizeof(svoh_frame_view) * (size_t)n_ref_frames, cur_frame, sizeof(svoh_frame_view) * (size_t)n_cur);
-      ctx->staged_views_resolved.assign(reinterpret_cast<const uint8_t*>(views), reinterpret_cast<const uint8_t*>(views) + sizeof(DevFrameView) * (size_t)(n_ref_frames + n_cur));
-      ctx->staged_views_ref_levels = ref_levels; ctx->staged_views_max_w = max_w; ctx->staged_views_max_h = max_h;
-      ctx->staged_views_generation = ctx->handle_generation;
-    }
-  }
-  if (whole_sets) {   // the units are the reference frames' features, frame after frame: where each frame's units begin
-    long long begin = 0;
-    for (int k = 0; k < n_ref_frames; ++k) { views[k].unit_begin = (int32_t)begin; begin += views[k].feat_n; }
-    SVOH_REQUIRE(ctx, begin == n, "SVOH_BATCH_WHOLE_SETS: the reference frames' resident sets do not add up to the batch's n");
-  }
-  ctx->matcher_deferred_used[kind] = true;
-  st.valid = false;   // consumed: the outputs stay readable, a second batch needs a new svoh_matcher_stage
-  SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d, h, st.in_total));
-  int g8 = n <= kG8MaxUnits ? 1 : 2;
-  g8 = SvohKnobs::or_default(ctx->knobs.matcher_g8, g8);
-  if (g8 < 0 || g8 > 3) g8 = 0;
-  if (g8 == 3) g8 = 1;
-  MatcherArgs a;
-  memset(&a, 0, sizeof a);
-  a.ref_frames = reinterpret_cast<const DevFrameView*>(d + st.o_views);
-  a.cur_frame = a.ref_frames + n_ref_frames;
-  a.mopt = *mopt;
-  if (dopt) a.dopt = *dopt;
-  a.n = n; a.n_ref_frames = n_ref_frames; a.n_cur_frames = n_cur;
-  a.whole_sets = whole_sets ? 1 : 0;
-  a.ref_frame_idx = reinterpret_cast<const int32_t*>(d + st.o_idx);
-  a.cur_frame_idx = reinterpret_cast<const int32_t*>(d + st.o_cidx);
-  a.px = reinterpret_cast<const double*>(d + st.o_px); a.f = reinterpret_cast<const double*>(d + st.o_f);
-  a.grad = reinterpret_cast<const double*>(d + st.o_grad); a.level = reinterpret_cast<const int32_t*>(d + st.o_level);
-  a.type = d + st.o_type;
-  a.result = reinterpret_cast<int32_t*>(d + st.o_result);
-  a.success = d + st.o_success;
-  if (st.want_outputs) {
-    a.f_cur = reinterpret_cast<double*>(d + st.o_fcur); a.search_level = reinterpret_cast<int32_t*>(d + st.o_slevel);
-    a.h_inv = reinterpret_cast<double*>(d + st.o_hinv); a.A_cur_ref = reinterpret_cast<double*>(d + st.o_A);
-  }
-  if (seeds) {
-    a.state = reinterpret_cast<double*>(d + st.o_state);
-    a.px_cur = st.want_outputs ? reinterpret_cast<double*>(d + st.o_pxcur) : nullptr;
-  } else {
-    a.depth = reinterpret_cast<const double*>(d + st.o_depth);
-    a.px_cur = reinterpret_cast<double*>(d + st.o_pxcur);
-  }
-  svoh_ctx::DeferredLaunch& dl = ctx->matcher_deferred_launch[kind];
-  dl.args.assign(reinterpret_cast<const uint8_t*>(&a), reinterpret_cast<const uint8_t*>(&a) + sizeof a);
-  dl.n = n; dl.g8 = g8; dl.valid = true; dl.max_w = max_w; dl.max_h = max_h;
-  dl.d_block = d; dl.out_off = st.in_total; dl.out_bytes = st.o_nsucc - st.in_total;
-  dl.d2h_dst = h + st.back_from; dl.d2h_src = d + st.back_from; dl.d2h_bytes = st.o_nsucc - st.back_from;
-  dl.views_h = h + st.o_views; dl.views_d = d + st.o_views; dl.n_ref = n_ref_frames; dl.n_cur = n_cur;
-  dl.cur_frame_handle = cur_frame[0].frame;
-  dl.pose_from_results = pose_from_results; dl.d_pose_results = pose_from_results ? ctx->d_pose_results : nullptr; dl.n_pose_results = ctx->n_pose_results;
-  dl.d_fidx = st.resident ? d + st.o_fidx : nullptr;
-  dl.seed_block_staged = seeds;
-  if (seeds && n_success) ctx->matcher_pending_counts.push_back({ n_success, h + st.o_success, n });
-  return SVOH_OK;
-}
 
 // ---- the candidate projections of many current frames in one launch (svoh_project_candidates_stage / ...) ----------
 struct MultiCandidateArgs {
@@ -4433,28 +4234,25 @@ try {
   svoh_ctx::MatcherStage& st = ctx->matcher_stage[kind];
   SVOH_REQUIRE(ctx, (flags & ~(SVOH_STAGE_MATCH_OUTPUTS | SVOH_STAGE_RESIDENT_COLUMNS)) == 0, "unknown flag");
   if (seeds) ctx->seed_block.valid = false;   // (its uploads are stream-ordered behind whatever still reads the old block)
-  layout_matcher_stage(seeds != 0, n, max_frame_views, (flags & SVOH_STAGE_MATCH_OUTPUTS) != 0, (flags & SVOH_STAGE_RESIDENT_COLUMNS) != 0, &st);
+  st.n = n; st.max_views = max_frame_views;
+  st.want_outputs = (flags & SVOH_STAGE_MATCH_OUTPUTS) != 0 || !seeds;
+  st.resident = (flags & SVOH_STAGE_RESIDENT_COLUMNS) != 0;
+  MatcherBlock& b = st.block;
+  b = MatcherBlock();
+  layout_matcher_stage(b, seeds != 0, (size_t)n, (size_t)max_frame_views, sizeof(DevFrameView), st.want_outputs, st.resident);
   PinnedBuffer& hbuf = seeds ? ctx->h_match_seeds : ctx->h_match_direct;
   DevBuffer& dbuf = seeds ? ctx->d_match_seeds : ctx->d_match_direct;
-  SVOH_HIP_TRY(ctx, hbuf.reserve(st.total));
-  SVOH_HIP_TRY(ctx, dbuf.reserve(st.total));
+  SVOH_HIP_TRY(ctx, hbuf.reserve(b.total));
+  SVOH_HIP_TRY(ctx, dbuf.reserve(b.total));
   uint8_t* h = static_cast<uint8_t*>(hbuf.ptr);
+  // every member at its column of the pinned block, NULL where the block has none (or has it on the device only)
+  const auto hand_out = [&](auto*& p, MatcherSlot s) { p = static_cast<std::remove_reference_t<decltype(p)>>(b.staged(h, s)); };
   memset(out, 0, sizeof *out);
-  out->ref_frame_idx = reinterpret_cast<int32_t*>(h + st.o_idx); out->cur_frame_idx = reinterpret_cast<int32_t*>(h + st.o_cidx);
-  if (st.resident) out->feature_index = reinterpret_cast<int32_t*>(h + st.o_fidx);
-  else {
-    out->px = reinterpret_cast<double*>(h + st.o_px); out->f = reinterpret_cast<double*>(h + st.o_f); out->grad = reinterpret_cast<double*>(h + st.o_grad);
-    out->level = reinterpret_cast<int32_t*>(h + st.o_level);
-  }
-  out->type = h + st.o_type;
-  out->result = reinterpret_cast<int32_t*>(h + st.o_result); out->success = h + st.o_success;
-  if (seeds) out->state = reinterpret_cast<double*>(h + st.o_state);
-  else { out->depth = reinterpret_cast<double*>(h + st.o_depth); out->px_cur = reinterpret_cast<double*>(h + st.o_pxcur); }
-  if (st.want_outputs) {
-    if (seeds) out->px_cur = reinterpret_cast<double*>(h + st.o_pxcur);
-    out->f_cur = reinterpret_cast<double*>(h + st.o_fcur); out->search_level = reinterpret_cast<int32_t*>(h + st.o_slevel);
-    out->h_inv = reinterpret_cast<double*>(h + st.o_hinv); out->A_cur_ref = reinterpret_cast<double*>(h + st.o_A);
-  }
+  hand_out(out->ref_frame_idx, kSlotRefIdx); hand_out(out->cur_frame_idx, kSlotCurIdx); hand_out(out->feature_index, kSlotFeatIdx);
+  hand_out(out->px, kSlotPx); hand_out(out->f, kSlotF); hand_out(out->grad, kSlotGrad); hand_out(out->level, kSlotLevel);
+  hand_out(out->type, kSlotType); hand_out(out->depth, kSlotDepth); hand_out(out->px_cur, kSlotPxCur); hand_out(out->state, kSlotState);
+  hand_out(out->result, kSlotResult); hand_out(out->success, kSlotSuccess); hand_out(out->f_cur, kSlotFCur);
+  hand_out(out->search_level, kSlotSearchLevel); hand_out(out->h_inv, kSlotHInv); hand_out(out->A_cur_ref, kSlotA);
   st.valid = true;
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
@@ -4532,80 +4330,73 @@ static int launch_deferred(svoh_ctx* ctx)
 {
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   SVOH_ALIGN_JOIN(ctx);
-  {
-    svoh_ctx::DeferredLaunch& d0 = ctx->matcher_deferred_launch[0];
-    svoh_ctx::DeferredLaunch& d1 = ctx->matcher_deferred_launch[1];
-    const bool v0 = d0.valid, v1 = d1.valid;
-    d0.valid = d1.valid = false;
-    if (v0 || v1) {
-      MatcherArgs a0, a1;
-      memset(&a0, 0, sizeof a0); memset(&a1, 0, sizeof a1);
-      if (v0) memcpy(&a0, d0.args.data(), sizeof a0);
-      if (v1) memcpy(&a1, d1.args.data(), sizeof a1);
-      const size_t n0 = v0 ? (size_t)d0.n : 0, n1 = v1 ? (size_t)d1.n : 0;
-      unsigned long long* dummy;
-      unsigned int* uc = nullptr;
-      int rc = reset_counters(ctx, &dummy);
-      if (rc == SVOH_OK) rc = reserve_unit_counts(ctx, n0 + n1, &uc);
-      if (rc != SVOH_OK) return rc;
-      a0.unit_counts = uc; a1.unit_counts = uc + 4 * n0;
-      auto blocks = [](const svoh_ctx::DeferredLaunch& d) { const int u = d.g8 ? 8 : 64; return (unsigned)((d.n + u - 1) / u); };   // per-unit geometries 0 / 1
-      // poses composed on the device and features named by index: one small launch ahead of the kernels that read them
-      {
-        auto prologue_of = [](const svoh_ctx::DeferredLaunch& d, const MatcherArgs& a, bool valid) {
-          PrologueBatch b;
-          memset(&b, 0, sizeof b);
-          const bool gather = d.d_fidx && !(a.whole_sets && d.g8 == 2);   // (whole sets in the packed geometry: the kernel reads the resident columns itself)
-          if (!valid || (!gather && !d.pose_from_results)) return b;
-          b.views = static_cast<DevFrameView*>(d.views_d); b.n_ref = d.n_ref; b.n_cur = d.n_cur;
-          if (gather) {
-            b.n = d.n; b.ref_idx = const_cast<int32_t*>(a.ref_frame_idx); b.fidx = static_cast<const int32_t*>(d.d_fidx);
-            b.whole_sets = a.whole_sets;
-            b.px = const_cast<double*>(a.px); b.f = const_cast<double*>(a.f); b.grad = const_cast<double*>(a.grad); b.level = const_cast<int32_t*>(a.level);
-          }
-          if (d.pose_from_results) { b.pose_results = static_cast<const svoh_pose_result*>(d.d_pose_results); b.n_pose_results = d.n_pose_results; }
-          return b;
-        };
-        const PrologueBatch b0 = prologue_of(d0, a0, v0), b1 = prologue_of(d1, a1, v1);
-        auto blocks_of = [](const PrologueBatch& b) { const int m = std::max(b.fidx ? b.n : 0, b.pose_results ? b.n_cur : 0); return (m + 255) / 256; };
-        const int nb0 = blocks_of(b0), nb1 = blocks_of(b1);
-        if (nb0 + nb1 > 0) hipLaunchKernelGGL(matcher_prologue_kernel, dim3((unsigned)(nb0 + nb1)), dim3(256), 0, ctx->stream, b0, b1, nb0);
-        d0.pose_from_results = d1.pose_from_results = false; d0.d_fidx = d1.d_fidx = nullptr;
+  svoh_ctx::DeferredLaunch& d0 = ctx->matcher_deferred_launch[0];
+  svoh_ctx::DeferredLaunch& d1 = ctx->matcher_deferred_launch[1];
+  const bool v0 = d0.valid, v1 = d1.valid;
+  d0.valid = d1.valid = false;
+  if (!v0 && !v1) return SVOH_OK;
+  MatcherArgs a0, a1;
+  memset(&a0, 0, sizeof a0); memset(&a1, 0, sizeof a1);
+  if (v0) memcpy(&a0, d0.args.data(), sizeof a0);
+  if (v1) memcpy(&a1, d1.args.data(), sizeof a1);
+  const size_t n0 = v0 ? (size_t)d0.n : 0, n1 = v1 ? (size_t)d1.n : 0;
+  unsigned int* uc = nullptr;
+  // poses composed on the device and features named by index: one small launch ahead of the kernels that read them
+  const auto prologue = [&] {
+    a0.unit_counts = uc; a1.unit_counts = uc + 4 * n0;
+    auto prologue_of = [](const svoh_ctx::DeferredLaunch& d, const MatcherArgs& a, bool valid) {
+      PrologueBatch b;
+      memset(&b, 0, sizeof b);
+      const bool gather = d.d_fidx && !(a.whole_sets && d.g8 == kGeomPacked);   // (whole sets in the packed geometry: the kernel reads the resident columns itself)
+      if (!valid || (!gather && !d.pose_from_results)) return b;
+      b.views = static_cast<DevFrameView*>(d.views_d); b.n_ref = d.n_ref; b.n_cur = d.n_cur;
+      if (gather) {
+        b.n = d.n; b.ref_idx = const_cast<int32_t*>(a.ref_frame_idx); b.fidx = static_cast<const int32_t*>(d.d_fidx);
+        b.whole_sets = a.whole_sets;
+        b.px = const_cast<double*>(a.px); b.f = const_cast<double*>(a.f); b.grad = const_cast<double*>(a.grad); b.level = const_cast<int32_t*>(a.level);
       }
-      if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_start, ctx->stream));
-      if (v0 && v1 && d0.g8 == d1.g8 && d0.g8 != 2) {
-        const unsigned b0 = blocks(d0), b1 = blocks(d1);
-        if (d0.g8) hipLaunchKernelGGL(match_mixed_kernel<true>, dim3(b0 + b1), dim3(64), 0, ctx->stream, a0, a1, (int)b0);
-        else hipLaunchKernelGGL(match_mixed_kernel<false>, dim3(b0 + b1), dim3(64), 0, ctx->stream, a0, a1, (int)b0);
-      } else {
-        // (the packed geometry's kernels do not write the optional outputs of units that return early: zeroed here)
-        if (v0) {
-          if (d0.g8 == 2 && d0.out_bytes) SVOH_HIP_TRY(ctx, hipMemsetAsync(static_cast<uint8_t*>(d0.d_block) + d0.out_off, 0, d0.out_bytes, ctx->stream));
-          rc = launch_matcher_kernels(ctx, false, d0.g8, a0, d0.n, a0.n_ref_frames, d0.max_w, d0.max_h);
-          if (rc != SVOH_OK) return rc;
-        }
-        if (v1) {
-          if (d1.g8 == 2 && d1.out_bytes) SVOH_HIP_TRY(ctx, hipMemsetAsync(static_cast<uint8_t*>(d1.d_block) + d1.out_off, 0, d1.out_bytes, ctx->stream));
-          rc = launch_matcher_kernels(ctx, true, d1.g8, a1, d1.n, a1.n_ref_frames, d1.max_w, d1.max_h);
-          if (rc != SVOH_OK) return rc;
-        }
-      }
-      SVOH_HIP_TRY(ctx, hipGetLastError());
-      if (ctx->timing_on()) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_misc_stop, ctx->stream));
-      ctx->misc_timed = ctx->timing_on(); ctx->misc_launched = true;
-      rc = reduce_unit_counts(ctx, n0 + n1);
-      if (rc != SVOH_OK) return rc;
-      if (v0) SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, d0.d2h_dst, d0.d2h_src, d0.d2h_bytes));
-      if (v1) SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, d1.d2h_dst, d1.d2h_src, d1.d2h_bytes));
-      // what collect waits for: these copies, not whatever the caller queues on the stream afterwards
-      if (!ctx->ev_matcher_done) SVOH_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_matcher_done, hipEventDisableTiming));
-      SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_matcher_done, ctx->stream));
-      ctx->matcher_done_recorded = true;
-      if (v1 && a1.state) {   // a seed batch of the section (staged or from host arrays): its device block can serve svoh_align_camera::pos_seed_unit until it is laid out anew
-        svoh_ctx::SeedBlock& sb = ctx->seed_block;
-        sb.valid = true; sb.views = a1.ref_frames; sb.n_ref = a1.n_ref_frames; sb.ref_idx = a1.ref_frame_idx; sb.f = a1.f; sb.state = a1.state; sb.n = d1.n;
-      }
+      if (d.pose_from_results) { b.pose_results = static_cast<const svoh_pose_result*>(d.d_pose_results); b.n_pose_results = d.n_pose_results; }
+      return b;
+    };
+    const PrologueBatch b0 = prologue_of(d0, a0, v0), b1 = prologue_of(d1, a1, v1);
+    auto blocks_of = [](const PrologueBatch& b) { const int m = std::max(b.fidx ? b.n : 0, b.pose_results ? b.n_cur : 0); return (m + 255) / 256; };
+    const int nb0 = blocks_of(b0), nb1 = blocks_of(b1);
+    if (nb0 + nb1 > 0) hipLaunchKernelGGL(matcher_prologue_kernel, dim3((unsigned)(nb0 + nb1)), dim3(256), 0, ctx->stream, b0, b1, nb0);
+    d0.pose_from_results = d1.pose_from_results = false; d0.d_fidx = d1.d_fidx = nullptr;
+    return (int)SVOH_OK;
+  };
+  const auto kernels = [&] {
+    if (v0 && v1 && d0.g8 == d1.g8 && d0.g8 != kGeomPacked) {
+      const unsigned b0 = (unsigned)((d0.n + units_per_block(d0.g8) - 1) / units_per_block(d0.g8));   // (per-unit geometries: one lane or eight)
+      const unsigned b1 = (unsigned)((d1.n + units_per_block(d1.g8) - 1) / units_per_block(d1.g8));
+      if (d0.g8 != kGeomOneLane) hipLaunchKernelGGL(match_mixed_kernel<true>, dim3(b0 + b1), dim3(64), 0, ctx->stream, a0, a1, (int)b0);
+      else hipLaunchKernelGGL(match_mixed_kernel<false>, dim3(b0 + b1), dim3(64), 0, ctx->stream, a0, a1, (int)b0);
+      return (int)SVOH_OK;
     }
+    // (the packed geometry's kernels do not write the optional outputs of units that return early: zeroed here)
+    if (v0) {
+      if (d0.g8 == kGeomPacked && d0.out_bytes) SVOH_HIP_TRY(ctx, hipMemsetAsync(static_cast<uint8_t*>(d0.d_block) + d0.out_off, 0, d0.out_bytes, ctx->stream));
+      const int rc = launch_matcher_kernels(ctx, false, d0.g8, a0, d0.n, a0.n_ref_frames, d0.max_w, d0.max_h);
+      if (rc != SVOH_OK) return rc;
+    }
+    if (v1) {
+      if (d1.g8 == kGeomPacked && d1.out_bytes) SVOH_HIP_TRY(ctx, hipMemsetAsync(static_cast<uint8_t*>(d1.d_block) + d1.out_off, 0, d1.out_bytes, ctx->stream));
+      const int rc = launch_matcher_kernels(ctx, true, d1.g8, a1, d1.n, a1.n_ref_frames, d1.max_w, d1.max_h);
+      if (rc != SVOH_OK) return rc;
+    }
+    return (int)SVOH_OK;
+  };
+  const int rc = launch_bracket(ctx, n0 + n1, &uc, kernels, prologue);
+  if (rc != SVOH_OK) return rc;
+  if (v0) SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, d0.d2h_dst, d0.d2h_src, d0.d2h_bytes));
+  if (v1) SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, d1.d2h_dst, d1.d2h_src, d1.d2h_bytes));
+  // what collect waits for: these copies, not whatever the caller queues on the stream afterwards
+  if (!ctx->ev_matcher_done) SVOH_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_matcher_done, hipEventDisableTiming));
+  SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_matcher_done, ctx->stream));
+  ctx->matcher_done_recorded = true;
+  if (v1 && a1.state) {   // a seed batch of the section (staged or from host arrays): its device block can serve svoh_align_camera::pos_seed_unit until it is laid out anew
+    svoh_ctx::SeedBlock& sb = ctx->seed_block;
+    sb.valid = true; sb.views = a1.ref_frames; sb.n_ref = a1.n_ref_frames; sb.ref_idx = a1.ref_frame_idx; sb.f = a1.f; sb.state = a1.state; sb.n = d1.n;
   }
   return SVOH_OK;
 }
@@ -4702,8 +4493,10 @@ int svoh_match_direct_batch(svoh_ctx* ctx, const svoh_matcher_options* options, 
                             const svoh_feature_batch* features, const double* depth, double* px_cur, int32_t* result,
                             double* f_cur, int32_t* search_level, double* h_inv, double* A_cur_ref)
 try {
-  return run_matcher(ctx, false, options, nullptr, n_ref_frames, ref_frames, cur_frame, features, depth, px_cur, result,
-                     f_cur, search_level, h_inv, A_cur_ref, nullptr, nullptr, nullptr, nullptr, true);
+  MatcherArrays c;
+  c.depth = depth; c.px_cur = px_cur; c.result = result;
+  c.f_cur = f_cur; c.search_level = search_level; c.h_inv = h_inv; c.A_cur_ref = A_cur_ref;
+  return run_matcher(ctx, kEntryMatchDirect, options, nullptr, n_ref_frames, ref_frames, cur_frame, features, c);
 } SVOH_ABI_CATCH(ctx)
 
 int svoh_match_direct_batch_pixelwise(svoh_ctx* ctx, const svoh_matcher_options* options, int n_ref_frames,
@@ -4714,8 +4507,10 @@ int svoh_match_direct_batch_pixelwise(svoh_ctx* ctx, const svoh_matcher_options*
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, landmark_xyz, "landmark_xyz is NULL (svoh_match_direct_batch is the affine warp)");
-  return run_matcher(ctx, false, options, nullptr, n_ref_frames, ref_frames, cur_frame, features, depth, px_cur, result,
-                     f_cur, search_level, h_inv, A_cur_ref, nullptr, nullptr, nullptr, landmark_xyz, true);
+  MatcherArrays c;
+  c.depth = depth; c.landmark_xyz = landmark_xyz; c.px_cur = px_cur; c.result = result;
+  c.f_cur = f_cur; c.search_level = search_level; c.h_inv = h_inv; c.A_cur_ref = A_cur_ref;
+  return run_matcher(ctx, kEntryMatchPixelwise, options, nullptr, n_ref_frames, ref_frames, cur_frame, features, c);
 } SVOH_ABI_CATCH(ctx)
 
 int svoh_update_seeds_batch(svoh_ctx* ctx, const svoh_matcher_options* matcher_options,
@@ -4724,8 +4519,9 @@ int svoh_update_seeds_batch(svoh_ctx* ctx, const svoh_matcher_options* matcher_o
                             const svoh_feature_batch* features, double* state, uint8_t* success, int32_t* match_result,
                             int32_t* n_success)
 try {
-  return run_matcher(ctx, true, matcher_options, options, n_ref_frames, ref_frames, cur_frame, features, nullptr, nullptr,
-                     match_result, nullptr, nullptr, nullptr, nullptr, state, success, n_success, nullptr, true);
+  MatcherArrays c;
+  c.state = state; c.success = success; c.result = match_result; c.n_success = n_success;
+  return run_matcher(ctx, kEntryUpdateSeeds, matcher_options, options, n_ref_frames, ref_frames, cur_frame, features, c);
 } SVOH_ABI_CATCH(ctx)
 
 int svoh_update_seeds_chain(svoh_ctx* ctx, const svoh_matcher_options* matcher_options, const svoh_depth_filter_options* options,
@@ -4744,10 +4540,10 @@ int svoh_update_seeds_batch_ex(svoh_ctx* ctx, const svoh_matcher_options* matche
                                const svoh_feature_batch* features, double* state, uint8_t* success,
                                int32_t* match_result, int32_t* n_success, const svoh_seed_match_outputs* outputs)
 try {
-  const svoh_seed_match_outputs none = { nullptr, nullptr, nullptr, nullptr };
-  const svoh_seed_match_outputs& o = outputs ? *outputs : none;
-  return run_matcher(ctx, true, matcher_options, options, n_ref_frames, ref_frames, cur_frame, features, nullptr, o.px_cur,
-                     match_result, o.f_cur, o.search_level, nullptr, o.A_cur_ref, state, success, n_success);
+  MatcherArrays c;
+  c.state = state; c.success = success; c.result = match_result; c.n_success = n_success;
+  if (outputs) { c.px_cur = outputs->px_cur; c.f_cur = outputs->f_cur; c.search_level = outputs->search_level; c.A_cur_ref = outputs->A_cur_ref; }
+  return run_matcher(ctx, kEntryUpdateSeedsEx, matcher_options, options, n_ref_frames, ref_frames, cur_frame, features, c);
 } SVOH_ABI_CATCH(ctx)
 
 }  // extern "C"

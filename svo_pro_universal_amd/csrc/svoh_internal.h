@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/svo_hip.h"
+#include "svoh_matcher_block.h"
 
 namespace svoh {
 
@@ -333,7 +334,8 @@ struct svoh_ctx {
   std::vector<PendingCount> matcher_pending_counts;
   struct DeferredLaunch {              // a matcher launch waiting for svoh_matcher_collect (kernel arguments as bytes)
     std::vector<uint8_t> args;
-    int n = 0, g8 = 0;
+    int n = 0;
+    svoh::MatcherGeometry g8 = svoh::kGeomOneLane;
     int max_w = 0, max_h = 0;          // largest reference frame (the packed geometry's spatial bins)
     size_t out_off = 0, out_bytes = 0; // packed geometry: the batch's output area in its device block, zeroed ahead of the kernel
     void* d_block = nullptr;
@@ -346,7 +348,6 @@ struct svoh_ctx {
     const void* d_pose_results = nullptr; int n_pose_results = 0; bool pose_from_results = false;
     // features named by index (svoh_feature_batch::feature_index): gathered from the reference frames' resident columns ahead of the kernels
     const void* d_fidx = nullptr;
-    bool seed_block_staged = false;    // a staged seed batch (its device block can serve svoh_align_camera::pos_seed_unit after the flush)
   } matcher_deferred_launch[2];
   // staging of the deferred batches, one pair per kind: nothing else stages through them, so any other call made
   // inside the section (a device-resident batch, an epipolar batch, the detector -- all on d_scratch1 / h_scratch1)
@@ -357,9 +358,7 @@ struct svoh_ctx {
   struct MatcherStage {
     bool valid = false, want_outputs = false, resident = false;
     int n = 0, max_views = 0;
-    size_t o_fidx = 0;
-    size_t o_views = 0, o_idx = 0, o_cidx = 0, o_px = 0, o_f = 0, o_grad = 0, o_level = 0, o_type = 0, o_depth = 0, o_pxcur = 0, o_state = 0,
-           o_result = 0, o_success = 0, o_fcur = 0, o_slevel = 0, o_hinv = 0, o_A = 0, o_nsucc = 0, in_total = 0, back_from = 0, total = 0;
+    svoh::MatcherBlock block;          // layout_matcher_stage (svoh_matcher_block.h)
   } matcher_stage[2];
 
   // candidate projection of the reprojector (svoh_project_candidates_enqueue / _collect): its own staging pair -- the
