@@ -178,6 +178,9 @@ def align_pyr_2d(pyr_ref, pyr_cur, max_level, min_level, patch_sizes, n_iter, mi
             if np.isnan(u) or np.isnan(v):
                 return False, tuple(px_cur)
             go_to_next_level = False
+            if np.isinf(u) or np.isinf(v):        # (int)floorf(+-inf) is no pixel of any image; Python's int() would raise
+                go_to_next_level = True
+                break
             u_r, v_r = int(np.floor(u)), int(np.floor(v))
             if u_r < 0 or v_r < 0 or u_r >= width - P or v_r >= height - P:
                 go_to_next_level = True
@@ -196,9 +199,10 @@ def align_pyr_2d(pyr_ref, pyr_cur, max_level, min_level, patch_sizes, n_iter, mi
             res = interp - tmpl
             Jres0, Jres1 = f32(-(res * dx).sum()), f32(-(res * dy).sum())
             assert abs((res * dx).sum()) < 2 ** 24 and abs((res * dy).sum()) < 2 ** 24
-            up0 = f32(f32(f32(Hi00 * Jres0) + f32(Hi01 * Jres1)) * f32(2.0))
-            up1 = f32(f32(f32(Hi10 * Jres0) + f32(Hi11 * Jres1)) * f32(2.0))
-            u, v = f32(u + up0), f32(v + up1)
+            with np.errstate(over="ignore", invalid="ignore"):      # a singular H: inf * 0 = NaN, as in the reference's floats
+                up0 = f32(f32(f32(Hi00 * Jres0) + f32(Hi01 * Jres1)) * f32(2.0))
+                up1 = f32(f32(f32(Hi10 * Jres0) + f32(Hi11 * Jres1)) * f32(2.0))
+                u, v = f32(u + up0), f32(v + up1)
             if f32(f32(up0 * up0) + f32(up1 * up1)) < f32(min_update_squared):
                 converged = True
                 break

@@ -33,6 +33,29 @@ import math
 import numpy as np
 
 f32 = np.float32
+f64 = np.float64
+
+
+# The reference divides in float / double: x / 0 is inf, 0 / 0 and inf - inf are NaN, and the values go on through the code
+# (a flat patch: H = 0, 1 / det = inf, the update NaN).  Python's float raises ZeroDivisionError and math.acos raises
+# ValueError where C returns inf / NaN, so every such operation is done on NumPy scalars, silently, as IEEE 754 defines it.
+def ieee(fn):
+    def silent(*args, **kw):
+        with np.errstate(all="ignore"):
+            return fn(*args, **kw)
+    silent.__name__, silent.__doc__ = fn.__name__, fn.__doc__
+    return silent
+
+
+def _acos(x):                          # C's acos: NaN outside [-1, 1] (and for a NaN); libm's value inside, as before
+    x = float(x)
+    return math.acos(x) if -1.0 <= x <= 1.0 else float("nan")
+
+
+def _sqrt(x):                          # C's sqrt: NaN below zero
+    x = float(x)
+    return math.sqrt(x) if x >= 0.0 else float("nan")
+
 
 # svo::FeatureType (src/svo_common/include/svo/common/types.h:60-73)
 EDGELET_SEED, CORNER_SEED, MAPPOINT_SEED = 0, 1, 2
@@ -165,6 +188,7 @@ class Cam(object):
         J[0, 1] = J[1, 0]
         return J
 
+    @ieee
     def undistort(self, x, y):            # :79-95: five fixed-point iterations
         if self.dist is None:
             return x, y
@@ -174,20 +198,22 @@ class Cam(object):
             xx, yy, xy = x * x, y * y, x * y
             xy2 = 2 * xy
             r2 = xx + yy
-            icdist = 1.0 / (1.0 + (k1 + k2 * r2) * r2)
+            icdist = f64(1.0) / f64(1.0 + (k1 + k2 * r2) * r2)
             dx = p1 * xy2 + p2 * (r2 + 2.0 * xx)
             dy = p2 * xy2 + p1 * (r2 + 2.0 * yy)
             x = (x0 - dx) * icdist
             y = (y0 - dy) * icdist
         return x, y
 
+    @ieee
     def project3(self, p):                # pinhole_projection.hpp:44-64
-        z_inv = 1.0 / p[2]
+        z_inv = f64(1.0) / f64(p[2])
         x, y = self.distort(p[0] * z_inv, p[1] * z_inv)
         return np.array([self.fx * x + self.cx, self.fy * y + self.cy])
 
+    @ieee
     def project3_jacobian(self, p):       # :55-63: diag(fx, fy) * J_dist(uv) * d(uv)/d(xyz)
-        z_inv = 1.0 / p[2]
+        z_inv = f64(1.0) / f64(p[2])
         uv = (p[0] * z_inv, p[1] * z_inv)
         duv = np.array([[z_inv, 0.0, -p[0] * z_inv * z_inv], [0.0, z_inv, -p[1] * z_inv * z_inv]])
         return np.diag([self.fx, self.fy]) @ self.distort_jacobian(uv[0], uv[1]) @ duv
@@ -220,6 +246,7 @@ class FrameView(object):
 # a-10 warp
 # ---------------------------------------------------------------------------------------------------------------
 
+@ieee
 def get_warp_matrix_affine(cam_ref, cam_cur, px_ref, f_ref, depth_ref, T_cur_ref, level_ref):
     """patch_warp.cpp:20-60 (pinhole branch: the back-projected rays are scaled by the z of xyz_ref)."""
     half = 5
@@ -247,10 +274,12 @@ def get_best_search_level(A_cur_ref, max_level):
 
 def inverse2(A):
     """Eigen's 2x2 inverse: adjugate times 1/det."""
-    invdet = 1.0 / (A[0, 0] * A[1, 1] - A[1, 0] * A[0, 1])
-    return np.array([[A[1, 1] * invdet, -A[0, 1] * invdet], [-A[1, 0] * invdet, A[0, 0] * invdet]])
+    with np.errstate(all="ignore"):
+        invdet = f64(1.0) / f64(A[0, 0] * A[1, 1] - A[1, 0] * A[0, 1])
+        return np.array([[A[1, 1] * invdet, -A[0, 1] * invdet], [-A[1, 0] * invdet, A[0, 0] * invdet]])
 
 
+@ieee
 def warp_affine(A_cur_ref, img_ref, px_ref, level_ref, search_level, halfpatch):
     """patch_warp.cpp:112-156: (2 halfpatch)^2 u8 patch (row-major) or None.  float32 sampling coordinates and
     weights, truncating float -> u8."""
@@ -284,6 +313,7 @@ def warp_affine(A_cur_ref, img_ref, px_ref, level_ref, search_level, halfpatch):
     return val.astype(np.uint8)                    # C's float -> uint8_t: truncation (values are in [0, 255])
 
 
+@ieee
 def warp_pixelwise(cur, ref, px_ref, landmark_pos, level_ref, level_cur, halfpatch):
     """patch_warp.cpp:158-230: (2 halfpatch)^2 u8 patch or None.  The patch's pixels (search level of the current frame)
     are back-projected to the landmark's distance from the current camera and sampled in the reference level; double
@@ -351,6 +381,7 @@ def _seq_sum(x):
     return np.cumsum(x.astype(f32), dtype=f32)[-1]
 
 
+@ieee
 def _inverse3_f32(m):
     """Eigen 3x3 inverse (InverseImpl.h: cofactors of column 0, det = their dot with column 0, transposed cofactors
     times 1/det), float32."""
@@ -368,6 +399,7 @@ def _inverse3_f32(m):
     return r
 
 
+@ieee
 def _inverse4_f32(m):
     """Eigen 4x4 inverse, generic (non-vectorised) path: signed cofactors, divided by the expansion along column 0."""
     def det3(i1, i2, i3, j1, j2, j3):
@@ -407,6 +439,7 @@ def _interp_patch(img, u_r, v_r, w):
     return (((w[0] * tl + w[1] * tr) + w[2] * bl) + w[3] * br).ravel()
 
 
+@ieee
 def align1d(cur_img, direction, pwb, patch, n_iter, affine_est_offset, affine_est_gain, px):
     """feature_alignment.cpp:31-209.  px: (u, v) double in; returns (converged, px_out (2,) double, h_inv)."""
     rows, cols = cur_img.shape
@@ -426,7 +459,7 @@ def align1d(cur_img, direction, pwb, patch, n_iter, affine_est_offset, affine_es
         H[1, 1] = f32(1.0)
     if not affine_est_gain:
         H[2, 2] = f32(1.0)
-    h_inv = 1.0 / float(H[0, 0]) * K_PATCH * K_PATCH
+    h_inv = float(f64(1.0) / f64(H[0, 0]) * K_PATCH * K_PATCH)      # 1.0 / H(0, 0): a flat patch gives inf
     Hinv = _inverse3_f32(H)
     mean_diff, alpha = f32(0.0), f32(1.0)
     u, v = f32(px[0]), f32(px[1])
@@ -466,6 +499,7 @@ def align1d(cur_img, direction, pwb, patch, n_iter, affine_est_offset, affine_es
     return converged, np.array([float(u), float(v)]), h_inv
 
 
+@ieee
 def align2d(cur_img, pwb, patch, n_iter, affine_est_offset, affine_est_gain, px):
     """feature_alignment.cpp:212-391.  Returns (converged, px_out)."""
     rows, cols = cur_img.shape
@@ -551,6 +585,8 @@ class Matcher(object):
         self.A_cur_ref = np.zeros((2, 2)); self.search_level = 0; self.reject = False
         self.px_cur = np.zeros(2); self.f_cur = np.zeros(3); self.h_inv = 0.0
         self.pwb = None; self.patch = None; self.epi_image = np.zeros(2); self.epi_length_pyramid = 0.0
+        self.scan_log = None     # a list: the scans append (step index, score) of every scored step and set scan_n_steps
+        self.scan_n_steps = 0
 
     # -- matcher.cpp:31-141
     def find_match_direct(self, ref, cur, px, f, grad, level, ftype, ref_depth, px_cur, landmark_pos=None):
@@ -620,12 +656,14 @@ class Matcher(object):
         return (int(px[0] / (1 << patch_level) + 0.5), int(px[1] / (1 << patch_level) + 0.5))
 
     # -- matcher.cpp:340-413
+    @ieee
     def scan_unit_plane(self, frame, A, B, C, score, patch_level, zmssd_best):
         o = self.options
         n_steps = int(self.epi_length_pyramid / 0.7)
-        step = (A[:2] / A[2] - B[:2] / B[2]) / n_steps
+        step = (A[:2] / A[2] - B[:2] / B[2]) / f64(n_steps)
         if n_steps > o.max_epi_search_steps:
             n_steps = o.max_epi_search_steps
+        self.scan_n_steps = n_steps
         uv_C = C[:2] / C[2]
         uv = uv_C.copy()
         uv_best = uv.copy()
@@ -648,6 +686,8 @@ class Matcher(object):
                         break
                 else:
                     z = score.score(img, pxi[0] - K_HALF_PATCH, pxi[1] - K_HALF_PATCH)
+                    if self.scan_log is not None:
+                        self.scan_log.append((i, z))
                     if z < zmssd_best:
                         zmssd_best = z
                         uv_best = uv.copy()
@@ -660,13 +700,15 @@ class Matcher(object):
         return frame.cam.project3(np.array([uv_best[0], uv_best[1], 1.0])), zmssd_best
 
     # -- matcher.cpp:415-488
+    @ieee
     def scan_unit_sphere(self, frame, A, B, C, score, patch_level, zmssd_best):
         o = self.options
         n_steps = int(self.epi_length_pyramid / 0.7)
         n_steps = o.max_epi_search_steps if n_steps > o.max_epi_search_steps else n_steps
         half_steps = n_steps // 2
+        self.scan_n_steps = n_steps
         f_A, f_B = normalized(A), normalized(B)
-        step = math.acos(float(f_A @ f_B)) / n_steps
+        step = float(f64(_acos(float(f_A @ f_B))) / f64(n_steps))
         axis = normalized(np.cross(f_B, f_A))
         f_C = normalized(C)
         f_best = f_C.copy()
@@ -687,6 +729,8 @@ class Matcher(object):
                         break
                 else:
                     z = score.score(img, pxi[0] - K_HALF_PATCH, pxi[1] - K_HALF_PATCH)
+                    if self.scan_log is not None:
+                        self.scan_log.append((i, z))
                     if z < zmssd_best:
                         zmssd_best = z
                         f_best = f.copy()
@@ -694,6 +738,7 @@ class Matcher(object):
         return frame.cam.project3(f_best), zmssd_best
 
     # -- matcher.cpp:157-241
+    @ieee
     def find_epipolar_match_direct(self, ref, cur, T_cur_ref, px, f, grad, level, ftype, d_estimate_inv, d_min_inv, d_max_inv):
         """Returns (result, depth)."""
         o = self.options
@@ -703,7 +748,7 @@ class Matcher(object):
         B = rf + T_cur_ref.t * d_max_inv
         px_A, px_B = cur.cam.project3(A), cur.cam.project3(B)
         self.epi_image = px_A - px_B
-        self.A_cur_ref = get_warp_matrix_affine(ref.cam, cur.cam, px, f, 1.0 / max(0.000001, d_estimate_inv), T_cur_ref, level)
+        self.A_cur_ref = get_warp_matrix_affine(ref.cam, cur.cam, px, f, 1.0 / max(0.000001, d_estimate_inv), T_cur_ref, level)   # >= 1e-6
         self.reject = False
         if is_edgelet(ftype) and o.epi_search_edgelet_filtering:
             grad_cur = normalized(self.A_cur_ref @ grad)
@@ -741,6 +786,7 @@ class Matcher(object):
         return FAIL_SCORE, 0.0
 
 
+@ieee
 def depth_from_triangulation(T_search_ref, f_ref, f_cur):
     """matcher.cpp:492-505."""
     A = np.stack([q_rot(T_search_ref.q, f_ref), f_cur], axis=1)      # 3 x 2
@@ -755,26 +801,29 @@ def depth_from_triangulation(T_search_ref, f_ref, f_cur):
 # a-14 depth filter
 # ---------------------------------------------------------------------------------------------------------------
 
+@ieee
 def norm_pdf(x, mean, sigma):          # vikit/math_utils.h:186-194
-    e = x - mean
+    e = f64(x) - f64(mean)
     e *= -e
-    e /= 2 * sigma * sigma
-    r = math.exp(e)
-    r /= sigma * math.sqrt(2 * math.pi)
-    return r
+    e /= 2 * f64(sigma) * f64(sigma)
+    r = f64(math.exp(float(e)))         # e <= 0 or NaN: no overflow
+    r /= f64(sigma) * math.sqrt(2 * math.pi)
+    return float(r)
 
 
+@ieee
 def update_filter_vogiatzis(z, tau2, mu_range, st):
     """depth_filter.cpp:501-552; st = [mu, sigma2, a, b], updated in place; returns bool."""
-    mu, sigma2, a, b = st
+    mu, sigma2, a, b = [f64(x) for x in st]
+    z, tau2, one = f64(z), f64(tau2), f64(1.0)
     s = sigma2 + tau2
-    norm_scale = math.sqrt(s) if s >= 0 else float("nan")
+    norm_scale = _sqrt(s)
     if math.isnan(norm_scale):
         return False
     oldsigma2 = sigma2
-    s2 = 1.0 / (1.0 / sigma2 + 1.0 / tau2)
+    s2 = one / (one / sigma2 + one / tau2)
     m = s2 * (mu / sigma2 + z / tau2)
-    uniform_x = 1.0 / mu_range
+    uniform_x = one / f64(mu_range)
     C1 = a / (a + b) * norm_pdf(z, mu, norm_scale)
     C2 = b / (a + b) * uniform_x
     nc = C1 + C2
@@ -794,35 +843,38 @@ def update_filter_vogiatzis(z, tau2, mu_range, st):
     if mu < 0.0:
         mu = 1.0
         ok = False
-    st[:] = [mu, sigma2, a, b]
+    st[:] = [float(mu), float(sigma2), float(a), float(b)]
     return ok
 
 
+@ieee
 def update_filter_gaussian(z, tau2, st):
     """depth_filter.cpp:554-578."""
-    mu, sigma2 = st[0], st[1]
+    mu, sigma2, z, tau2 = f64(st[0]), f64(st[1]), f64(z), f64(tau2)
     s = sigma2 + tau2
     if s < 0 or math.isnan(s):
         return False
-    st[0] = (sigma2 * z + tau2 * mu) / s
-    st[1] = sigma2 * tau2 / s
+    st[0] = float((sigma2 * z + tau2 * mu) / s)
+    st[1] = float(sigma2 * tau2 / s)
     return True
 
 
+@ieee
 def compute_tau(T_ref_cur, f, z, px_error_angle):
     """depth_filter.cpp:580-596."""
     t = T_ref_cur.t
     a = f * z - t
-    t_norm = math.sqrt(float(t @ t))
-    a_norm = math.sqrt(float(a @ a))
-    alpha = math.acos(float(f @ t) / t_norm)
-    beta = math.acos(float(a @ (-t)) / (t_norm * a_norm))
+    t_norm = f64(_sqrt(float(t @ t)))
+    a_norm = f64(_sqrt(float(a @ a)))
+    alpha = _acos(f64(f @ t) / t_norm)
+    beta = _acos(f64(a @ (-t)) / (t_norm * a_norm))
     beta_plus = beta + px_error_angle
     gamma_plus = math.pi - alpha - beta_plus
-    z_plus = t_norm * math.sin(beta_plus) / math.sin(gamma_plus)
-    return z_plus - z
+    z_plus = t_norm * f64(math.sin(beta_plus)) / f64(math.sin(gamma_plus))      # the angles are finite or NaN
+    return float(z_plus - z)
 
 
+@ieee
 def update_seed(cur, ref, px, f, grad, level, ftype, st, matcher, sigma2_convergence_threshold, px_error_angle,
                 check_visibility=True, check_convergence=False, use_vogiatzis_update=True):
     """depth_filter_utils::updateSeed (depth_filter.cpp:367-499).  st: 4 doubles, updated in place.
@@ -835,7 +887,7 @@ def update_seed(cur, ref, px, f, grad, level, ftype, st, matcher, sigma2_converg
         return False, ftype, NOT_RUN
     T_cur_ref = cur.T_f_w * ref.T_f_w.inverse()
     if check_visibility:
-        xyz_f = T_cur_ref.apply((1.0 / st[0]) * f)                   # seed::getDepth = 1 / mu (seed.h:110-113)
+        xyz_f = T_cur_ref.apply(float(f64(1.0) / f64(st[0])) * f)                   # seed::getDepth = 1 / mu (seed.h:110-113)
         pxp = cur.cam.project3(xyz_f)
         if not (pxp[0] == pxp[0] and pxp[1] == pxp[1]) or not cur.cam.is_keypoint_visible(pxp):
             return False, ftype, NOT_RUN
@@ -844,7 +896,7 @@ def update_seed(cur, ref, px, f, grad, level, ftype, st, matcher, sigma2_converg
             return False, ftype, NOT_RUN
     matcher.options.align_1d = ftype in (EDGELET_SEED, EDGELET_SEED_CONV)
     # seed.h:115-128: inverse depth, mu + sigma, max(mu - sigma, 1e-8)
-    sig = math.sqrt(st[1]) if st[1] >= 0 else float("nan")
+    sig = _sqrt(st[1])
     res, depth = matcher.find_epipolar_match_direct(ref, cur, T_cur_ref, px, f, grad, level, ftype, st[0], st[0] + sig,
                                                     max(st[0] - sig, 0.00000001))
     if res != SUCCESS:
@@ -852,13 +904,13 @@ def update_seed(cur, ref, px, f, grad, level, ftype, st, matcher, sigma2_converg
             st[3] += 1                                                # seed::increaseOutlierProbability
         return False, ftype, res
     depth_sigma = compute_tau(T_cur_ref.inverse(), f, depth, px_error_angle)
-    z = 1.0 / depth                                                   # seed::getMeanFromDepth
-    sg = 0.5 * (1.0 / max(0.000000000001, depth - depth_sigma) - 1.0 / (depth + depth_sigma))   # getSigma2FromDepthSigma
+    z = float(f64(1.0) / f64(depth))                                             # seed::getMeanFromDepth
+    sg = float(0.5 * (f64(1.0) / f64(max(0.000000000001, depth - depth_sigma)) - f64(1.0) / f64(depth + depth_sigma)))   # getSigma2FromDepthSigma
     tau2 = sg * sg
     ok = update_filter_vogiatzis(z, tau2, ref.seed_mu_range, st) if use_vogiatzis_update else update_filter_gaussian(z, tau2, st)
     if not ok:
         return False, OUTLIER, res
-    thresh = ref.seed_mu_range / sigma2_convergence_threshold          # seed::isConverged (seed.h:143-151)
+    thresh = float(f64(ref.seed_mu_range) / f64(sigma2_convergence_threshold))         # seed::isConverged (seed.h:143-151)
     new_type = ftype
     if st[1] < thresh * thresh:
         new_type = {CORNER_SEED: CORNER_SEED_CONV, EDGELET_SEED: EDGELET_SEED_CONV, MAPPOINT_SEED: MAPPOINT_SEED_CONV}.get(ftype, ftype)

@@ -13,6 +13,8 @@ TOOL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp", "matcher_
 
 
 def _cases():
+    # built here, as the other tools of tests/cpp are by their tests: a tree whose tests/ holds sources only still runs this
+    subprocess.check_call(["make", "-s", "-C", os.path.dirname(TOOL), os.path.basename(TOOL)])
     out = subprocess.check_output([TOOL], text=True)
     cases, cur = [], None
     for line in out.splitlines():
