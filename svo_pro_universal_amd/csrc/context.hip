@@ -488,13 +488,10 @@ try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   const int timing = ctx->knobs.kernel_timing, copy_policy = ctx->knobs.copy_kernel;
   // the alignment plans its launches from these: both of its lanes run empty first (svoh_internal.h, launch lanes)
-  if (ctx->align_lane_stream) {
+  if (ctx->aq.has_lanes()) {
     SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
     SVOH_ALIGN_JOIN(ctx);
-    SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->align_lane_stream));
-    ctx->align_lane1_pending = false;
-    ctx->align_chain = false;
+    SVOH_HIP_TRY(ctx, ctx->aq.sync_lanes());
   }
   load_knobs_from_env(ctx->knobs);
   if (ctx->knobs.kernel_timing == kKnobUnset) ctx->knobs.kernel_timing = timing;   // set by svoh_set_kernel_timing, not by the environment
@@ -520,11 +517,7 @@ try {
   load_knobs_from_env(ctx->knobs);
   e = hipSetDevice(device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-  for (int k = 0; k < svoh_ctx::kAlignEventRing; ++k) {
-    if (e == hipSuccess) e = hipEventCreate(&ctx->ev_align_start[k]);
-    if (e == hipSuccess) e = hipEventCreate(&ctx->ev_align_stop[k]);
-  }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_align_staged, hipEventDisableTiming);
+  if (e == hipSuccess) e = ctx->aq.create(ctx->stream);
   if (e == hipSuccess) e = hipEventCreate(&ctx->ev_misc_start);
   if (e == hipSuccess) e = hipEventCreate(&ctx->ev_misc_stop);
   hipDeviceProp_t prop;
@@ -546,22 +539,12 @@ try {
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) { (void)hipStreamSynchronize(ctx->stream); }
   if (ctx->upload_stream) { (void)hipStreamSynchronize(ctx->upload_stream); }
-  // the alignment's copy stream: results of launches nobody fetched may still be on their way to h_results (a copy that was
-  // held back, svoh_internal.h, is dropped)
-  // (both lanes first: a copy queued on the copy stream waits for an event behind a kernel on one of them)
-  if (ctx->align_lane_stream) { (void)hipStreamSynchronize(ctx->align_lane_stream); }
-  if (ctx->align_copy_stream) { (void)hipStreamSynchronize(ctx->align_copy_stream); (void)hipStreamDestroy(ctx->align_copy_stream); }
-  if (ctx->align_lane_stream) { (void)hipStreamDestroy(ctx->align_lane_stream); }
-  for (hipEvent_t ev : { ctx->ev_align_kernel[0], ctx->ev_align_kernel[1], ctx->ev_align_uploaded, ctx->ev_align_delivered, ctx->ev_align_front, ctx->ev_align_lane1 })
-    if (ev) (void)hipEventDestroy(ev);
+  // the alignment's copy stream: results of launches nobody fetched may still be on their way to h_results
+  ctx->aq.teardown();
   ctx->frames.clear();
   for (auto& kv : ctx->masks) (void)hipFree(kv.second.ptr);
   ctx->masks.clear();
-  for (int k = 0; k < svoh_ctx::kAlignEventRing; ++k) {
-    if (ctx->ev_align_start[k]) (void)hipEventDestroy(ctx->ev_align_start[k]);
-    if (ctx->ev_align_stop[k]) (void)hipEventDestroy(ctx->ev_align_stop[k]);
-  }
-  if (ctx->ev_align_staged) (void)hipEventDestroy(ctx->ev_align_staged);
+  ctx->aq.destroy_events();
   if (ctx->ev_misc_start) (void)hipEventDestroy(ctx->ev_misc_start);
   if (ctx->ev_misc_stop) (void)hipEventDestroy(ctx->ev_misc_stop);
   if (ctx->ev_pose_done) (void)hipEventDestroy(ctx->ev_pose_done);
@@ -584,13 +567,8 @@ const char* svoh_last_error_string(const svoh_ctx* ctx)
 int svoh_synchronize(svoh_ctx* ctx)
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   // both lanes of the alignment: a launch on the second one is not on the context's stream
-  if (ctx->align_lane_stream) {
-    SVOH_HIP_TRY(ctx, hipStreamSynchronize(ctx->align_lane_stream));
-    ctx->align_lane1_pending = false;
-  }
-  ctx->align_chain = false;
+  SVOH_HIP_TRY(ctx, ctx->aq.sync_lanes());
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
 
@@ -598,7 +576,7 @@ try {
 void* svoh_stream(svoh_ctx* ctx)
 {
   if (!ctx) return nullptr;
-  (void)svoh::align_join_lanes(ctx);
+  (void)ctx->aq.join();
   return (void*)ctx->stream;
 }
 
@@ -960,9 +938,9 @@ try {
   size_t fb = 0;
   for (const auto& kv : slabs) fb += kv.second;
   out->frame_bytes = (int64_t)fb;
-  const svoh::DevBuffer* bufs[] = { &ctx->d_desc[0], &ctx->d_desc[1], &ctx->d_results, &ctx->d_feat, &ctx->d_eval, &ctx->d_xchg, &ctx->d_split,
+  const svoh::DevBuffer* bufs[] = { &ctx->d_xchg, &ctx->d_split,
                                     &ctx->d_counters, &ctx->d_unit_counts, &ctx->d_scratch0, &ctx->d_scratch1, &ctx->d_scratch2, &ctx->d_seed_bin, &ctx->d_match_seeds, &ctx->d_match_direct, &ctx->d_cand, &ctx->d_cand_multi, &ctx->d_seed_chain };
-  size_t wb = 0;
+  size_t wb = ctx->aq.reported_device_bytes();
   for (const svoh::DevBuffer* b : bufs) wb += b->cap;
   out->workspace_bytes = (int64_t)wb;
   return SVOH_OK;

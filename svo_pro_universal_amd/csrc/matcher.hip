@@ -3714,7 +3714,7 @@ static int enqueue_candidates(svoh_ctx* ctx, const svoh_camera* cam, const svoh_
   SVOH_REQUIRE(ctx, ctx->cand_pending_n == 0, "a candidate projection is queued already: collect first");
   if (align_result_index >= 0) {
     SVOH_REQUIRE(ctx, T_b != nullptr, "T_post is NULL");
-    SVOH_REQUIRE(ctx, (size_t)align_result_index < ctx->align_pending_results && (size_t)align_result_index < ctx->align_result_dev_index.size() && ctx->d_results.ptr,
+    SVOH_REQUIRE(ctx, ctx->aq.has_queued_result((size_t)align_result_index),
                  "no queued alignment result with this index");
   }
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3735,7 +3735,7 @@ static int enqueue_candidates(svoh_ctx* ctx, const svoh_camera* cam, const svoh_
   memset(&a, 0, sizeof a);
   a.cam = *cam; a.T_a = *T_a;
   if (T_b) a.T_b = *T_b;
-  a.align_result = align_result_index >= 0 ? static_cast<const svoh_align_result*>(ctx->d_results.ptr) + ctx->align_result_dev_index[(size_t)align_result_index] : nullptr;
+  a.align_result = align_result_index >= 0 ? ctx->aq.queued_result((size_t)align_result_index) : nullptr;
   a.T_world_kf = reinterpret_cast<const svoh_se3*>(d + o_kf);
   a.kind = d + o_kind; a.kf = reinterpret_cast<const int32_t*>(d + o_idx);
   a.v = reinterpret_cast<const double*>(d + o_v); a.mu = reinterpret_cast<const double*>(d + o_mu);
@@ -4140,9 +4140,9 @@ static int enqueue_staged_candidates(svoh_ctx* ctx, bool with_units)
     SVOH_REQUIRE(ctx, jb.n_points >= 0 && jb.point_begin >= 0 && (int64_t)jb.point_begin + jb.n_points <= st.n_points, "a job's point range leaves the arrays");
     dev_idx[j] = 0;
     if (jb.align_result_index >= 0) {
-      SVOH_REQUIRE(ctx, (size_t)jb.align_result_index < ctx->align_pending_results && (size_t)jb.align_result_index < ctx->align_result_dev_index.size() && ctx->d_results.ptr,
+      SVOH_REQUIRE(ctx, ctx->aq.has_queued_result((size_t)jb.align_result_index),
                    "no queued alignment result with this index");
-      dev_idx[j] = ctx->align_result_dev_index[(size_t)jb.align_result_index];
+      dev_idx[j] = ctx->aq.queued_result_index((size_t)jb.align_result_index);
       any_result = true;
     }
   }
@@ -4165,7 +4165,7 @@ static int enqueue_staged_candidates(svoh_ctx* ctx, bool with_units)
     memset(&a, 0, sizeof a);
     a.jobs = reinterpret_cast<const svoh_candidate_job*>(d + st.o_jobs);
     a.result_dev_index = reinterpret_cast<const uint32_t*>(a.jobs + st.n_jobs);
-    a.align_results = any_result ? static_cast<const svoh_align_result*>(ctx->d_results.ptr) : nullptr;
+    a.align_results = any_result ? ctx->aq.device_results() : nullptr;
     a.T_world_kf = reinterpret_cast<const svoh_se3*>(d + st.o_kf);
     a.ranges = reinterpret_cast<const DevCandidateRange*>(d + st.o_dev_ranges);
     a.kind = d + st.o_kind; a.mu = reinterpret_cast<const double*>(d + st.o_mu);
@@ -4186,7 +4186,7 @@ static int enqueue_staged_candidates(svoh_ctx* ctx, bool with_units)
   memset(&a, 0, sizeof a);
   a.jobs = reinterpret_cast<const svoh_candidate_job*>(d + st.o_jobs);
   a.result_dev_index = reinterpret_cast<const uint32_t*>(a.jobs + st.n_jobs);
-  a.align_results = any_result ? static_cast<const svoh_align_result*>(ctx->d_results.ptr) : nullptr;
+  a.align_results = any_result ? ctx->aq.device_results() : nullptr;
   a.T_world_kf = reinterpret_cast<const svoh_se3*>(d + st.o_kf);
   a.job = reinterpret_cast<const int32_t*>(d + st.o_job); a.kind = d + st.o_kind; a.kf = reinterpret_cast<const int32_t*>(d + st.o_idx);
   a.v = reinterpret_cast<const double*>(d + st.o_v); a.mu = reinterpret_cast<const double*>(d + st.o_mu);

@@ -40,59 +40,50 @@
 // (and every copy of results that went, or still has to go, over the alignment's copy stream has arrived: align_drain)
 // (and both launch lanes are empty.  SVOH_ALIGN_JOIN, svoh_internal.h, is the wait on the DEVICE that goes with it: the context's
 // stream waits for the launch on the second lane -- what every entry outside enqueue_align does before it uses that stream)
-#define SVOH_ALIGN_DRAIN(ctx) SVOH_HIP_TRY(ctx, svoh::align_drain(ctx))
+#define SVOH_ALIGN_DRAIN(ctx) SVOH_HIP_TRY(ctx, (ctx)->aq.drain())
 
 namespace svoh {
-
-static hipError_t align_drain(svoh_ctx* ctx);
 
 // Side copies (svoh_internal.h): the copy stream and its events, made ONCE per context, by its first launch of the kind that can
 // take the side path.  The runtime sets a stream up, and a copy engine for each direction, when they are first used -- milliseconds
 // that belong here and not beside a kernel: the head of the launch's staged block (h, at most 1 MB of it) goes up to its device
 // block d and the same bytes come back.  Nothing in flight may read d meanwhile: launches queued ahead are waited for.
-static hipError_t align_side_setup(svoh_ctx* ctx, void* h, void* d, size_t bytes)
+hipError_t AlignQueue::side_setup(void* h, void* d, size_t bytes)
 {
-  if (ctx->align_copy_stream) return hipSuccess;
-  hipError_t e = ctx->align_launches_since_drain ? align_drain(ctx) : hipSuccess;
-  hipEvent_t* evs[] = { &ctx->ev_align_kernel[0], &ctx->ev_align_kernel[1], &ctx->ev_align_uploaded, &ctx->ev_align_delivered };
+  if (copy_stream) return hipSuccess;
+  hipError_t e = align_busy(q) ? drain() : hipSuccess;
+  hipEvent_t* evs[] = { &ev_kernel[0], &ev_kernel[1], &ev_uploaded, &ev_delivered };
   for (hipEvent_t* ev : evs)
     if (e == hipSuccess && !*ev) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->align_copy_stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking);
   if (bytes > ((size_t)1 << 20)) bytes = (size_t)1 << 20;
-  if (e == hipSuccess) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->align_copy_stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->align_copy_stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->align_copy_stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, copy_stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, copy_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(copy_stream);
   return e;
 }
 
-// the copy of a side launch's results that was held back goes onto the copy stream, behind that launch's kernel
-static hipError_t align_flush_download(svoh_ctx* ctx)
+hipError_t AlignQueue::flush_download()
 {
-  svoh_ctx::AlignDownload& d = ctx->align_download;
-  if (!d.bytes) return hipSuccess;
-  hipError_t e = hipStreamWaitEvent(ctx->align_copy_stream, d.after, 0);
-  if (e == hipSuccess) e = hipMemcpyAsync(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost, ctx->align_copy_stream);
-  if (e == hipSuccess) e = hipEventRecord(ctx->ev_align_delivered, ctx->align_copy_stream);
+  if (!download.bytes) return hipSuccess;
+  hipError_t e = hipStreamWaitEvent(copy_stream, download.after, 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(download.dst, download.src, download.bytes, hipMemcpyDeviceToHost, copy_stream);
+  if (e == hipSuccess) e = hipEventRecord(ev_delivered, copy_stream);
   if (e != hipSuccess) return e;
-  d.bytes = 0;
-  ctx->align_delivery_pending = true;
+  download.bytes = 0;
+  delivery_pending = true;
   return hipSuccess;
 }
 
-// every launch has run (its upload with it: the kernel waits for it) and every result is in h_results
-static hipError_t align_drain(svoh_ctx* ctx)
+hipError_t AlignQueue::drain()
 {
-  hipError_t e = align_flush_download(ctx);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess && ctx->align_lane_stream) e = hipStreamSynchronize(ctx->align_lane_stream);
-  if (e == hipSuccess && ctx->align_delivery_pending) e = hipEventSynchronize(ctx->ev_align_delivered);
+  hipError_t e = flush_download();
+  if (e == hipSuccess) e = hipStreamSynchronize(main);
+  if (e == hipSuccess && lane_stream) e = hipStreamSynchronize(lane_stream);
+  if (e == hipSuccess && delivery_pending) e = hipEventSynchronize(ev_delivered);
   if (e != hipSuccess) return e;
-  ctx->align_lane1_pending = false;
-  ctx->align_chain = false;
-  ctx->align_last_lane = 0;
-  ctx->align_delivery_pending = false;
-  ctx->align_launches_since_drain = 0;
-  ctx->align_block_read_ev[0] = ctx->align_block_read_ev[1] = nullptr;
+  delivery_pending = false;
+  q = align_drained(q);
   return hipSuccess;
 }
 
@@ -101,17 +92,17 @@ static hipError_t align_drain(svoh_ctx* ctx)
 // warm-up, and the runtime sets a stream up when it is first used.  A few bytes of the launch's staged block go up to its device
 // block and come back on the new stream; launches queued ahead are waited for.  (The lane's WORKSPACE is not made here: a context
 // whose launches are never queued behind one another never needs it.)
-static hipError_t align_lane_setup(svoh_ctx* ctx, void* h, void* d, size_t bytes)
+hipError_t AlignQueue::lane_setup(void* h, void* d, size_t bytes)
 {
-  if (ctx->align_lane_stream) return hipSuccess;
-  hipError_t e = ctx->align_launches_since_drain ? align_drain(ctx) : hipSuccess;
-  if (e == hipSuccess && !ctx->ev_align_lane1) e = hipEventCreateWithFlags(&ctx->ev_align_lane1, hipEventDisableTiming);
-  if (e == hipSuccess && !ctx->ev_align_front) e = hipEventCreateWithFlags(&ctx->ev_align_front, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->align_lane_stream, hipStreamNonBlocking);
+  if (lane_stream) return hipSuccess;
+  hipError_t e = align_busy(q) ? drain() : hipSuccess;
+  if (e == hipSuccess && !ev_lane1) e = hipEventCreateWithFlags(&ev_lane1, hipEventDisableTiming);
+  if (e == hipSuccess && !ev_front) e = hipEventCreateWithFlags(&ev_front, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&lane_stream, hipStreamNonBlocking);
   if (bytes > 4096) bytes = 4096;
-  if (e == hipSuccess) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->align_lane_stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, ctx->align_lane_stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->align_lane_stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, lane_stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, lane_stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(lane_stream);
   return e;
 }
 
@@ -1962,23 +1953,184 @@ static double ref_extrinsics_deviation(const svoh_align_camera& cam)
   return dev;
 }
 
-static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_problems,
-                         const svoh_align_problem* problems, int eval_level, const SplitArgs* split = nullptr,
-                         const AlignGeometry* forced = nullptr)
+// ---- what the narrow and the wide entry do alike: a camera's checks, its descriptor, its arrays, the kernel arguments ----------
+
+static_assert(kAlignWsPairs == kWsPairs, "svoh_align_block.h restates the workspace's pairs per slot");
+// (the sizes tests/cpp/align_block_cpu.cpp lays its blocks out with)
+static_assert(sizeof(DevProblemDesc) == 192 && sizeof(DevCamDesc) == 696 && sizeof(PosFromSeedsJob) == 24, "tests/cpp/align_block_cpu.cpp and tests/align_block_layout.py name these sizes");
+
+// a camera's frame handles, their pyramid levels and its reference extrinsics, in that order; *fr / *fc: the two frames
+static int check_align_camera(svoh_ctx* ctx, const svoh_align_camera& cam, int p, int c, int need_levels, const Frame** fr, const Frame** fc)
 {
-  if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  *fr = find_frame(ctx, cam.ref_frame);
+  *fc = find_frame(ctx, cam.cur_frame);
+  if (!*fr || !*fc) return set_error(ctx, SVOH_ERR_BAD_HANDLE, "problem %d camera %d: unknown frame handle", p, c);
+  if ((*fr)->n_levels < need_levels || (*fc)->n_levels < need_levels)
+    return set_error(ctx, SVOH_ERR_INVALID_ARGUMENT, "problem %d camera %d: pyramid has fewer than %d levels", p, c, need_levels);
+  const double dev = ref_extrinsics_deviation(cam);
+  if (!(dev <= 1e-9))
+    return set_error(ctx, SVOH_ERR_INVALID_ARGUMENT,
+                     "problem %d camera %d: ref_T_cam_imu is not the inverse of ref_T_imu_cam (deviation %.3g)", p, c, dev);
+  return SVOH_OK;
+}
+
+// where the kernel finds a camera's four columns: the caller's device arrays, or the camera's uploaded piece at device address d
+struct CamColumns { const double* px; const double* f; const double* pos_world; const uint8_t* flags; };
+static CamColumns caller_columns(const svoh_align_camera& cam) { return { cam.px, cam.f, cam.pos_world, cam.flags }; }
+static CamColumns uploaded_columns(const uint8_t* d, size_t n)
+{
+  const AlignCamColumns o(n);
+  return { reinterpret_cast<const double*>(d + o.px), reinterpret_cast<const double*>(d + o.f), reinterpret_cast<const double*>(d + o.pos), d + o.flags };
+}
+
+// the descriptor of share [lo, hi) of a camera, whose first feature takes slot feat_off of the workspace
+static void fill_cam_desc(DevCamDesc& dc, const svoh_align_camera& cam, const Frame& fr, const Frame& fc, const CamColumns& col, const AlignShare& sh, int feat_off)
+{
+  for (int l = 0; l < SVOH_MAX_LEVELS; ++l) {
+    dc.ref[l] = l < fr.n_levels ? fr.lv[l] : DevImage{ nullptr, 0, 0, 0, 0 };
+    dc.cur[l] = l < fc.n_levels ? fc.lv[l] : DevImage{ nullptr, 0, 0, 0, 0 };
+  }
+  dc.cam = cam.cam;
+  dc.ref_T_imu_cam = cam.ref_T_imu_cam;
+  dc.ref_T_cam_imu = cam.ref_T_cam_imu;
+  dc.cur_T_cam_imu = cam.cur_T_cam_imu;
+  for (int k = 0; k < 3; ++k) dc.ref_pos[k] = cam.ref_pos[k];
+  dc.n_features = (int32_t)sh.n();
+  dc.feat_off = feat_off;
+  dc.px = col.px + 2 * sh.lo; dc.f = col.f + 3 * sh.lo; dc.pos_world = col.pos_world + 3 * sh.lo; dc.flags = col.flags + sh.lo;
+}
+
+static void fill_problem_desc(DevProblemDesc& d, const svoh_align_problem& pb, int cam_begin)
+{
+  d.n_cams = pb.n_cams;
+  d.cam_begin = cam_begin;
+  d.T_init = pb.T_icur_iref;
+  d.alpha_init = pb.alpha_init; d.beta_init = pb.beta_init;
+  d.prior = pb.prior;
+}
+
+// a camera's host arrays into its piece of the pinned block
+static void gather_camera(uint8_t* h, const svoh_align_camera& cam, size_t n)
+{
+  if (!n) return;
+  const AlignCamColumns o(n);
+  memcpy(h + o.px, cam.px, n * 16);
+  memcpy(h + o.f, cam.f, n * 24);
+  memcpy(h + o.pos, cam.pos_world, n * 24);
+  memcpy(h + o.flags, cam.flags, n);
+}
+
+// What every launch of the resident kernel is told alike: the descriptors and the queue head in the device block d, the
+// workspace at w, where results and an evaluation's sums go.  Everything else is zero.
+static void base_kernel_args(AlignKernelArgs& args, const svoh_ctx* ctx, const AlignBlock& block, void* d, int n_desc, const AlignWorkspace& ws, void* w,
+                             svoh_align_result* results, const svoh_align_options* opt, int eval_level)
+{
+  memset(&args, 0, sizeof args);
+  uint8_t* const db = static_cast<uint8_t*>(d);
+  uint8_t* const wb = static_cast<uint8_t*>(w);
+  args.problems = reinterpret_cast<const DevProblemDesc*>(db);
+  args.cams = reinterpret_cast<const DevCamDesc*>(db + block.cams_off);
+  args.results = results;
+  args.wpk = reinterpret_cast<double*>(wb + ws.wpk_off);
+  args.slots = (int64_t)ws.slots;
+  args.wsel = wb + ws.wsel_off;
+  args.wvis = wb + ws.wvis_off;
+  args.opt = *opt;
+  args.eval_level = eval_level;
+  args.eval_out = static_cast<double*>(ctx->aq.d_eval.ptr);
+  args.n_problems = n_desc;
+  args.queue = reinterpret_cast<int32_t*>(db + block.ctl_off);   // zero: uploaded with the descriptors
+}
+
+// the rows of a small problem in LDS behind the image area (512-thread geometry)
+static int32_t ws_lds_bytes_for(int max_feat_per_problem)
+{
+  return ((max_feat_per_problem > 0 ? max_feat_per_problem : 1) * kWsPairs * 16 + 15) & ~15;
+}
+
+// Room for `want` results in one of the result queues (d_results, h_results), of which the first `keep` belong to launches queued
+// since the last fetch.  Nothing to keep: the buffer grows by its own rule.  Otherwise those launches still deliver into the old
+// block: let them finish, take theirs along into a block of twice the need.
+template <class Buffer, class Copy>
+static int reserve_results(svoh_ctx* ctx, Buffer& buf, size_t want, size_t keep, Copy&& copy)
+{
+  const size_t need = sizeof(svoh_align_result) * want;
+  if (need <= buf.cap) return SVOH_OK;
+  if (!keep) {
+    SVOH_HIP_TRY(ctx, buf.reserve(need));
+    return SVOH_OK;
+  }
+  SVOH_ALIGN_DRAIN(ctx);
+  Buffer bigger;
+  SVOH_HIP_TRY(ctx, bigger.reserve(need * 2));
+  SVOH_HIP_TRY(ctx, copy(bigger.ptr, buf.ptr, sizeof(svoh_align_result) * keep));
+  std::swap(bigger.ptr, buf.ptr);
+  std::swap(bigger.cap, buf.cap);
+  return SVOH_OK;
+}
+
+// ---- enqueue_align, step by step ---------------------------------------------------------------------------------------------
+
+// One call of enqueue_align: what its steps hand to one another.
+struct AlignCall {
+  svoh_ctx* ctx;
+  const svoh_align_options* opt;
+  int n_problems;
+  const svoh_align_problem* problems;
+  int eval_level;
+  const SplitArgs* split;
+  const AlignGeometry* forced;
+  AlignGeometry shared_single;
+  // size(): shares per problem, descriptors, the staged block
+  int S = 1, n_desc = 0;
+  bool cluster = false;
+  size_t n_cams_total = 0, n_feat_total = 0;
+  int n_pos_jobs = 0;    // cameras whose seed positions come from the seed batch in flight (svoh_align_camera::pos_seed_unit)
+  LaunchShape shape;     // largest problem (share); some problem has more than one camera; ... whose patches fill five to eight waves, camera by camera
+  AlignBlock block;
+  // take_blocks(): the descriptor slot, where the results go
+  unsigned slot = 0;
+  bool delivers = false;
+  size_t dev_results_off = 0;
+  // fill()
+  std::vector<PosFromSeedsJob> pos_jobs;
+  int pos_jobs_max_n = 0;
+  const PosFromSeedsJob* pos_jobs_device = nullptr;
+  // place_and_upload(): the geometry, the place in the queue
+  AlignGeometry geo;
+  bool lane_kind = false;
+  AlignLaunchPlan plan;
+  hipStream_t ks = nullptr;   // the launch's lane
+  AlignKernelArgs args;
+
+  // (a constructor, so that the argument block is filled once, by arguments(), and not cleared here as well)
+  AlignCall(svoh_ctx* ctx_, const svoh_align_options* opt_, int n_problems_, const svoh_align_problem* problems_, int eval_level_, const SplitArgs* split_,
+            const AlignGeometry* forced_)
+    : ctx(ctx_), opt(opt_), n_problems(n_problems_), problems(problems_), eval_level(eval_level_), split(split_), forced(forced_) {}
+  bool update() const { return split && split->update; }
+  int size();
+  int take_blocks();
+  int fill();
+  int place_and_upload();
+  void arguments();
+  int launch_update();
+  int launch();
+  int deliver();
+};
+
+// checks and sizes
+int AlignCall::size()
+{
   int rc = validate_options(ctx, opt);
   if (rc != SVOH_OK) return rc;
   SVOH_REQUIRE(ctx, n_problems >= 1 && problems, "no problems");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   // a launch of ONE problem under shared classes: the geometry its key names (svoh_set_align_geometry_classes)
-  AlignGeometry shared_single;
   if (!forced && !split && eval_level < 0 && n_problems == 1 && shared_class_geometry(ctx, problems[0], &shared_single)) forced = &shared_single;
 
   // patch-split evaluation: the one problem becomes S descriptors, share s holding features
   // [n*s/S, n*(s+1)/S) of every camera, one workgroup each
-  int S = (split && !split->update && split->n_shares > 1) ? split->n_shares : 1;
-  bool cluster = false;
+  S = (split && !split->update && split->n_shares > 1) ? split->n_shares : 1;
   if (!split && eval_level < 0) {
     const int g = forced ? forced->cluster_g : decide_cluster(ctx, n_problems, problems);
     if (g >= 2) { S = g; cluster = true; }
@@ -1987,12 +2139,8 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   SVOH_REQUIRE(ctx, !cluster || (int64_t)S * n_problems <= ctx->num_cus, "cluster mode: more workgroups than compute units");
   SVOH_REQUIRE(ctx, !cluster || n_problems <= kClusterMaxProblems, "cluster mode: more problems in one launch than arrival counters");
   SVOH_REQUIRE(ctx, S == 1 || n_problems == 1 || cluster, "shares apply to a single problem");
-  const int n_desc = n_problems * S;
+  n_desc = n_problems * S;
 
-  // pass 1: sizes
-  size_t n_cams_total = 0, n_feat_total = 0, host_bytes = 0;
-  int n_pos_jobs = 0;   // cameras whose seed positions come from the seed batch in flight (svoh_align_camera::pos_seed_unit)
-  LaunchShape shape;   // largest problem (share); some problem has more than one camera; ... whose patches fill five to eight waves, camera by camera
   for (int p = 0; p < n_problems; ++p) {
     const svoh_align_problem& pb = problems[p];
     SVOH_REQUIRE(ctx, pb.n_cams >= 1 && pb.n_cams <= SVOH_MAX_CAMS, "n_cams out of range");
@@ -2005,11 +2153,10 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
       SVOH_REQUIRE(ctx, cam.cam.distortion == SVOH_DISTORTION_NONE || cam.cam.distortion == SVOH_DISTORTION_RADTAN,
                    "unsupported distortion model");
       nf += cam.n_features;
-      if (cam.mem_space == SVOH_MEM_HOST && !(split && split->update))
-        host_bytes += ((size_t)cam.n_features * (8 * 8 + 1) + 63) & ~(size_t)63;
+      if (cam.mem_space == SVOH_MEM_HOST && !update()) block.size_camera((size_t)cam.n_features);
       if (cam.pos_seed_unit) {
         SVOH_REQUIRE(ctx, cam.mem_space == SVOH_MEM_HOST && !split && eval_level < 0, "pos_seed_unit: host-memory cameras of full runs only");
-        host_bytes += (((size_t)cam.n_features * 4 + 63) & ~(size_t)63) + 64;   // the units, and the camera's entry of the job table
+        block.size_seed_units((size_t)cam.n_features);   // the units, and the camera's entry of the job table
         ++n_pos_jobs;
       }
     }
@@ -2019,15 +2166,16 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   }
   SVOH_REQUIRE(ctx, n_pos_jobs == 0 || ctx->seed_block.valid,
                "pos_seed_unit: no staged seed batch has been sent off on this context (or its block has been staged again)");
-  const int max_feat_per_problem = shape.max_feat_per_problem;
-  const size_t feat_slots = n_feat_total ? n_feat_total : 1;
-
   // descriptors, then (256-byte aligned) the zeroed work-queue head and the cluster arrival counters, then the
   // feature arrays of host-resident cameras: one staging block, one upload
-  const size_t desc_only = sizeof(DevProblemDesc) * n_desc + sizeof(DevCamDesc) * n_cams_total;
-  const size_t ctl_off = (desc_only + 255) & ~(size_t)255;
-  const size_t up_base = ctl_off + 512;
-  const size_t desc_bytes = up_base + host_bytes;
+  block.lay_out((size_t)n_desc, n_cams_total, sizeof(DevProblemDesc), sizeof(DevCamDesc));
+  return SVOH_OK;
+}
+
+// the launch's descriptor blocks, and room in every buffer it writes but its workspace
+int AlignCall::take_blocks()
+{
+  AlignQueue& aq = ctx->aq;
   // The pinned staging buffer is reused by every call.  A call queued right behind another (enqueue without fetch,
   // the patch-split entries) must not write a byte of it -- not even the zeroed control block, whose offset moves
   // with the descriptor count and would land inside the earlier call's descriptors -- nor let reserve() replace
@@ -2036,314 +2184,227 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   // (the slot is committed only once the upload has been queued: a call that fails in between -- an unknown frame handle,
   // a failed reserve -- must leave the NEXT call on the block this one was about to use, not on the block the last
   // successful launch may still be uploading from)
-  const unsigned desc_slot = ctx->align_desc_slot ^ 1u;
-  PinnedBuffer& h_desc = desc_slot ? ctx->h_desc_odd : ctx->h_desc;
-  if (ctx->align_launches_since_drain >= 2) {
-    // this block was last read by the upload of the launch before the last one, which has not been waited for
-    if (ctx->align_staged_wait_ev) SVOH_HIP_TRY(ctx, hipEventSynchronize(ctx->align_staged_wait_ev));
-    else SVOH_ALIGN_DRAIN(ctx);
-  }
-  SVOH_HIP_TRY(ctx, h_desc.reserve(desc_bytes));
+  const AlignBlockPlace bp = place_block(aq.q);
+  slot = bp.slot;
+  // this block was last read by the upload of the launch before the last one, which has not been waited for
+  if (bp.wait == kAlignBlockWaitEvent) SVOH_HIP_TRY(ctx, hipEventSynchronize(aq.staged_wait_ev()));
+  else if (bp.wait == kAlignBlockDrain) SVOH_ALIGN_DRAIN(ctx);
+  PinnedBuffer& h_desc = aq.h_block(slot);
+  SVOH_HIP_TRY(ctx, h_desc.reserve(block.reserve));
   // the device block alternates with the pinned one: a launch queued behind another can be uploaded while that one's kernel
-  // reads the other block (below).  A block that must grow may still be read by the launch before the last one: drain first.
-  DevBuffer& d_desc = ctx->d_desc[desc_slot];
-  if (desc_bytes > d_desc.cap && ctx->align_launches_since_drain >= 1) SVOH_ALIGN_DRAIN(ctx);
-  SVOH_HIP_TRY(ctx, d_desc.reserve(desc_bytes));
-  memset(static_cast<uint8_t*>(h_desc.ptr) + ctl_off, 0, 512);
+  // reads the other block.  A block that must grow may still be read by the launch before the last one: drain first.
+  DevBuffer& d_desc = aq.d_desc[slot];
+  if (block.reserve > d_desc.cap && align_busy(aq.q)) SVOH_ALIGN_DRAIN(ctx);
+  SVOH_HIP_TRY(ctx, d_desc.reserve(block.reserve));
+  memset(static_cast<uint8_t*>(h_desc.ptr) + block.ctl_off, 0, kAlignCtlBytes);
   // results of launches queued since the last fetch are kept one after the other in pinned host memory -- and on the
   // device as well (a candidate projection queued behind several launches reads the result of any of them):
   // this launch's device block of n_desc + n_problems results starts behind the blocks of the launches before it
-  const bool delivers = (S == 1 || cluster) && eval_level < 0;
-  const size_t dev_results_off = delivers ? ctx->align_pending_dev : 0;
-  {
-    // (as for h_results below: the first launch of a queue makes room for a queue of launches of its size, so that the
-    // launches behind it do not drain the stream here to replace the block)
-    size_t want_dev = dev_results_off + (size_t)n_desc + n_problems;
-    if (delivers && dev_results_off == 0 && (size_t)svoh_ctx::kAlignEventRing * (size_t)n_problems <= svoh_ctx::kMaxQueuedResults)
-      want_dev *= (size_t)svoh_ctx::kAlignEventRing;
-    const size_t need = sizeof(svoh_align_result) * want_dev;
-    if (need > ctx->d_results.cap) {
-      if (dev_results_off) {   // earlier launches' results live in the old block: let them finish, take them along
-        SVOH_ALIGN_DRAIN(ctx);
-        DevBuffer bigger;
-        SVOH_HIP_TRY(ctx, bigger.reserve(need * 2));
-        SVOH_HIP_TRY(ctx, hipMemcpy(bigger.ptr, ctx->d_results.ptr, sizeof(svoh_align_result) * dev_results_off, hipMemcpyDeviceToDevice));
-        std::swap(bigger.ptr, ctx->d_results.ptr);
-        std::swap(bigger.cap, ctx->d_results.cap);
-      } else {
-        SVOH_HIP_TRY(ctx, ctx->d_results.reserve(need));
-      }
-    }
-  }
+  delivers = (S == 1 || cluster) && eval_level < 0;
+  dev_results_off = delivers ? aq.pending_dev : 0;
+  // room for a queue of launches of this size (AlignQueue::kEventRing of them), made by the first launch of a queue, so that a
+  // caller that queues steps back to back never waits here for the stream to drain and a block to be replaced
+  const size_t queue_of_these = (size_t)AlignQueue::kEventRing * (size_t)n_problems;
+  size_t want_dev = dev_results_off + (size_t)n_desc + n_problems;
+  if (delivers && dev_results_off == 0 && queue_of_these <= AlignQueue::kMaxQueuedResults) want_dev *= (size_t)AlignQueue::kEventRing;
+  int rc = reserve_results(ctx, aq.d_results, want_dev, dev_results_off,
+                           [](void* dst, const void* src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice); });
+  if (rc != SVOH_OK) return rc;
   if (delivers) {
-    SVOH_REQUIRE(ctx, ctx->align_pending_results + (size_t)n_problems <= svoh_ctx::kMaxQueuedResults,
+    SVOH_REQUIRE(ctx, aq.pending_results + (size_t)n_problems <= AlignQueue::kMaxQueuedResults,
                  "too many alignment results queued without a fetch");
-    // room for a queue of launches of this size (svoh_ctx::kAlignEventRing of them), so that a caller that queues
-    // steps back to back never waits here for the stream to drain and the block to be replaced
-    size_t want_results = ctx->align_pending_results + (size_t)n_problems;
-    const size_t queue_of_these = (size_t)svoh_ctx::kAlignEventRing * (size_t)n_problems;
-    if (want_results < queue_of_these && queue_of_these <= svoh_ctx::kMaxQueuedResults) want_results = queue_of_these;
-    const size_t need = sizeof(svoh_align_result) * want_results;
-    if (need > ctx->h_results.cap) {
-      if (ctx->align_pending_results) {   // earlier launches still deliver into the old block: let them finish, keep theirs
-        SVOH_ALIGN_DRAIN(ctx);
-        PinnedBuffer bigger;
-        SVOH_HIP_TRY(ctx, bigger.reserve(need * 2));
-        memcpy(bigger.ptr, ctx->h_results.ptr, sizeof(svoh_align_result) * ctx->align_pending_results);
-        std::swap(bigger.ptr, ctx->h_results.ptr);
-        std::swap(bigger.cap, ctx->h_results.cap);
-      } else {
-        SVOH_HIP_TRY(ctx, ctx->h_results.reserve(need));
-      }
-    }
+    size_t want_results = aq.pending_results + (size_t)n_problems;
+    if (want_results < queue_of_these && queue_of_these <= AlignQueue::kMaxQueuedResults) want_results = queue_of_these;
+    rc = reserve_results(ctx, aq.h_results, want_results, aq.pending_results,
+                         [](void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return hipSuccess; });
+    if (rc != SVOH_OK) return rc;
   }
-  SVOH_HIP_TRY(ctx, ctx->d_eval.reserve(74 * sizeof(double) * S));
+  SVOH_HIP_TRY(ctx, aq.d_eval.reserve(74 * sizeof(double) * S));
+  return SVOH_OK;
+}
 
-  DevProblemDesc* hp = static_cast<DevProblemDesc*>(h_desc.ptr);
-  DevCamDesc* hc = reinterpret_cast<DevCamDesc*>(hp + n_desc);
-  uint8_t* hup = static_cast<uint8_t*>(h_desc.ptr) + up_base;
-  uint8_t* dup = static_cast<uint8_t*>(d_desc.ptr) + up_base;
-  size_t up_off = 0;
+// the descriptors and the host cameras' arrays into the pinned block
+int AlignCall::fill()
+{
+  AlignQueue& aq = ctx->aq;
+  uint8_t* const h = static_cast<uint8_t*>(aq.h_block(slot).ptr);
+  uint8_t* const d = static_cast<uint8_t*>(aq.d_desc[slot].ptr);
+  DevProblemDesc* hp = reinterpret_cast<DevProblemDesc*>(h);
+  DevCamDesc* hc = reinterpret_cast<DevCamDesc*>(h + block.cams_off);
   int cam_idx = 0, feat_off = 0;
   const int need_levels = opt->max_level + 1;
-  const uint8_t* share_base[SVOH_MAX_CAMS] = {};   // uploaded block of camera c (host arrays, S > 1)
-  std::vector<PosFromSeedsJob> pos_jobs;
-  int pos_jobs_max_n = 0;
+  const uint8_t* share_base[SVOH_MAX_CAMS] = {};   // uploaded piece of camera c (host arrays, S > 1)
   for (int pd = 0; pd < n_desc; ++pd) {
     const int p = pd / S, sh = pd % S;
     const svoh_align_problem& pb = problems[p];
-    DevProblemDesc& d = hp[pd];
-    d.n_cams = pb.n_cams;
-    d.cam_begin = cam_idx;
-    d.T_init = pb.T_icur_iref;
-    d.alpha_init = pb.alpha_init; d.beta_init = pb.beta_init;
-    d.prior = pb.prior;
+    fill_problem_desc(hp[pd], pb, cam_idx);
     for (int c = 0; c < pb.n_cams; ++c, ++cam_idx) {
       const svoh_align_camera& cam = pb.cams[c];
-      DevCamDesc& dc = hc[cam_idx];
-      const Frame* fr = find_frame(ctx, cam.ref_frame);
-      const Frame* fc = find_frame(ctx, cam.cur_frame);
-      if (!fr || !fc) return set_error(ctx, SVOH_ERR_BAD_HANDLE, "problem %d camera %d: unknown frame handle", p, c);
-      if (fr->n_levels < need_levels || fc->n_levels < need_levels)
-        return set_error(ctx, SVOH_ERR_INVALID_ARGUMENT, "problem %d camera %d: pyramid has fewer than %d levels", p,
-                         c, need_levels);
-      for (int l = 0; l < SVOH_MAX_LEVELS; ++l) {
-        dc.ref[l] = l < fr->n_levels ? fr->lv[l] : DevImage{ nullptr, 0, 0, 0, 0 };
-        dc.cur[l] = l < fc->n_levels ? fc->lv[l] : DevImage{ nullptr, 0, 0, 0, 0 };
-      }
-      dc.cam = cam.cam;
-      {
-        const double dev = ref_extrinsics_deviation(cam);
-        if (!(dev <= 1e-9))
-          return set_error(ctx, SVOH_ERR_INVALID_ARGUMENT,
-                           "problem %d camera %d: ref_T_cam_imu is not the inverse of ref_T_imu_cam (deviation %.3g)", p, c, dev);
-      }
-      dc.ref_T_imu_cam = cam.ref_T_imu_cam;
-      dc.ref_T_cam_imu = cam.ref_T_cam_imu;
-      dc.cur_T_cam_imu = cam.cur_T_cam_imu;
-      for (int k = 0; k < 3; ++k) dc.ref_pos[k] = cam.ref_pos[k];
-      const size_t lo = (size_t)((int64_t)cam.n_features * sh / S), hi = (size_t)((int64_t)cam.n_features * (sh + 1) / S);
-      dc.n_features = (int32_t)(hi - lo);
-      dc.feat_off = feat_off;
-      feat_off += dc.n_features;
-      if (cam.mem_space == SVOH_MEM_DEVICE || cam.n_features == 0 || (split && split->update)) {
-        dc.px = cam.px + 2 * lo; dc.f = cam.f + 3 * lo; dc.pos_world = cam.pos_world + 3 * lo; dc.flags = cam.flags + lo;
-      } else {
-        const size_t n = (size_t)cam.n_features;
-        if (sh == 0) {   // the camera's arrays go up once; every share points into the same block
-          uint8_t* h = hup + up_off;
-          memcpy(h, cam.px, n * 16);
-          memcpy(h + n * 16, cam.f, n * 24);
-          memcpy(h + n * 40, cam.pos_world, n * 24);
-          memcpy(h + n * 64, cam.flags, n);
-          share_base[c] = dup + up_off;
-          up_off += (n * 65 + 63) & ~(size_t)63;
-        }
-        if (sh == 0 && cam.pos_seed_unit) {   // its units go up behind the camera's arrays; the job points at the uploaded positions
-          memcpy(hup + up_off, cam.pos_seed_unit, n * 4);
+      const Frame *fr, *fc;
+      const int rc = check_align_camera(ctx, cam, p, c, need_levels, &fr, &fc);
+      if (rc != SVOH_OK) return rc;
+      const size_t n = (size_t)cam.n_features;
+      const bool uploaded = !(cam.mem_space == SVOH_MEM_DEVICE || cam.n_features == 0 || update());
+      if (uploaded && sh == 0) {   // the camera's arrays go up once; every share points into the same piece
+        const size_t at = block.place_camera(n);
+        gather_camera(h + at, cam, n);
+        share_base[c] = d + at;
+        if (cam.pos_seed_unit) {   // its units go up behind the camera's arrays; the job points at the uploaded positions
+          const size_t at_units = block.place_seed_units(n);
+          memcpy(h + at_units, cam.pos_seed_unit, n * 4);
           PosFromSeedsJob jb;
-          jb.pos = reinterpret_cast<double*>(const_cast<uint8_t*>(share_base[c]) + n * 40);
-          jb.unit = reinterpret_cast<const int32_t*>(dup + up_off);
+          jb.pos = const_cast<double*>(uploaded_columns(share_base[c], n).pos_world);
+          jb.unit = reinterpret_cast<const int32_t*>(d + at_units);
           jb.n = (int32_t)n; jb.pad_ = 0;
           pos_jobs.push_back(jb);
           if ((int)n > pos_jobs_max_n) pos_jobs_max_n = (int)n;
-          up_off += (n * 4 + 63) & ~(size_t)63;
         }
-        const uint8_t* dv = share_base[c];
-        dc.px = reinterpret_cast<const double*>(dv) + 2 * lo;
-        dc.f = reinterpret_cast<const double*>(dv + n * 16) + 3 * lo;
-        dc.pos_world = reinterpret_cast<const double*>(dv + n * 40) + 3 * lo;
-        dc.flags = dv + n * 64 + lo;
       }
+      const AlignShare share(cam.n_features, sh, S);
+      fill_cam_desc(hc[cam_idx], cam, *fr, *fc, uploaded ? uploaded_columns(share_base[c], n) : caller_columns(cam), share, feat_off);
+      feat_off += (int)share.n();
     }
   }
-  const PosFromSeedsJob* pos_jobs_device = nullptr;
   if (!pos_jobs.empty()) {   // the job table rides the same upload
-    memcpy(hup + up_off, pos_jobs.data(), sizeof(PosFromSeedsJob) * pos_jobs.size());
-    pos_jobs_device = reinterpret_cast<const PosFromSeedsJob*>(dup + up_off);
-    up_off += (sizeof(PosFromSeedsJob) * pos_jobs.size() + 63) & ~(size_t)63;
+    const size_t at = block.place_job_table(pos_jobs.size(), sizeof(PosFromSeedsJob));
+    memcpy(h + at, pos_jobs.data(), sizeof(PosFromSeedsJob) * pos_jobs.size());
+    pos_jobs_device = reinterpret_cast<const PosFromSeedsJob*>(d + at);
   }
+  return SVOH_OK;
+}
+
+// The launch's place in the queue (place_launch, svoh_align_block.h), carried out up to its upload: which lane, beside the launch
+// before it or behind it, copies on the lane or on the copy stream.
+int AlignCall::place_and_upload()
+{
+  AlignQueue& aq = ctx->aq;
+  void* const h = aq.h_block(slot).ptr;
+  void* const d = aq.d_desc[slot].ptr;
   // Side copies (svoh_internal.h): a launch of the batch geometry queued behind an alignment launch that is still in flight
   // sends its block up on the copy stream, beside that launch's kernel, and its results down beside the next one's.  Every
   // other launch -- the first of a queue, small ones, keyed ones (a lock-step group: four groups share the hardware queues,
   // a side stream costs them more than it gives), evaluation, split -- keeps its copies on the context's stream.
   // The copy stream is made by the context's first launch of this kind, queued or not: a caller's first such launches are
-  // its warm-up, and the runtime's set-up of a stream and its copy engines takes milliseconds (align_side_setup).
+  // its warm-up, and the runtime's set-up of a stream and its copy engines takes milliseconds (side_setup).
   // By default only a block larger than the copy kernels' window (1 MB, copy_by_kernel in context.hip) goes there: a smaller one
   // travels by copy kernel on the context's stream with no hand-over to a copy engine at all, and the side path costs it more than
   // it saves (1024 frame pairs per step, 0.9 MB: 1.38 ms per step with side copies against 1.20 without,
   // profiles/r07_align_side_copies_ab.txt).  SVOH_ALIGN_SIDE_COPIES=1 sends every such launch there, =0 none.
   const int side_knob = ctx->knobs.align_side_copies;
   const bool side_kind = n_desc >= ctx->num_cus && !cluster && !split && !forced && eval_level < 0 &&
-                         (side_knob == kKnobUnset ? up_base + up_off > ((size_t)1 << 20) : side_knob != 0);
-  if (side_kind) SVOH_HIP_TRY(ctx, align_side_setup(ctx, h_desc.ptr, d_desc.ptr, up_base + up_off));
+                         align_side_wanted(side_knob != kKnobUnset, side_knob, block.used);
+  if (side_kind) SVOH_HIP_TRY(ctx, aq.side_setup(h, d, block.used));
   // Launch lanes (svoh_internal.h).  A launch of the batch geometry -- the 256-thread batch build over at least a workgroup per
   // compute unit; not a cluster, keyed, split or evaluation launch, none whose seed positions are gathered on the context's stream --
   // that comes right behind another such launch nobody has waited for, with nothing put on the context's stream in between
-  // (align_chain), takes the lane that launch did not take: its kernel starts as soon as compute units of the previous kernel
+  // (q.chain), takes the lane that launch did not take: its kernel starts as soon as compute units of the previous kernel
   // fall idle.  Everything else runs on lane 0, the context's stream, behind whatever runs on lane 1.
   // SVOH_ALIGN_OVERLAP=0: one lane.  On by default at every size of the batch geometry: 512 ... 4096 frame pairs per step all gain
   // (0.52 against 0.71 ms per step, 0.96 against 1.17, 2.03 against 2.21, 3.42 against 3.74: profiles/r08_align_overlap_ab.txt).
-  const AlignGeometry geo = forced ? *forced : decide_geometry(ctx, opt, n_desc, cluster ? S : 0, shape);
+  geo = forced ? *forced : decide_geometry(ctx, opt, n_desc, cluster ? S : 0, shape);
   SVOH_REQUIRE(ctx, !(geo.nt == 128 && shape.multi_cam), "the 128-thread geometry takes single-camera problems only");
   const int overlap_knob = ctx->knobs.align_overlap;
-  const bool lane_kind = n_desc >= ctx->num_cus && (geo.nt == 256 || geo.nt == 128) && !geo.latency && !cluster && !split && !forced && eval_level < 0 && n_pos_jobs == 0 &&
-                         (overlap_knob == kKnobUnset || overlap_knob != 0);
-  if (lane_kind) SVOH_HIP_TRY(ctx, align_lane_setup(ctx, h_desc.ptr, d_desc.ptr, up_base + up_off));
-  const size_t feat_bytes = feat_slots * (kWsPairs * 16 + 2) + 256;
-  {
-    // A lane's workspace grows as the single one did, sized by the largest launch the lane has seen; the second lane's is made by
-    // the context's first launch that takes that lane.  While one that is in use is replaced nothing runs on either lane (the
-    // launch is then the first of a new queue, on lane 0; the workspace it was headed for has grown all the same, for the next).
-    const bool to_lane1 = lane_kind && ctx->align_chain && ctx->align_launches_since_drain >= 1 && ctx->align_last_lane == 0;
-    DevBuffer& ws = to_lane1 ? ctx->d_feat_lane1 : ctx->d_feat;
-    if (ws.ptr && feat_bytes > ws.cap && ctx->align_launches_since_drain >= 1 && ctx->align_lane_stream && ctx->align_lane1_launches) {
-      SVOH_ALIGN_DRAIN(ctx);
-      SVOH_HIP_TRY(ctx, ws.reserve(feat_bytes));
-    }
+  lane_kind = n_desc >= ctx->num_cus && (geo.nt == 256 || geo.nt == 128) && !geo.latency && !cluster && !split && !forced && eval_level < 0 && n_pos_jobs == 0 &&
+              align_overlap_wanted(overlap_knob != kKnobUnset, overlap_knob);
+  if (lane_kind) SVOH_HIP_TRY(ctx, aq.lane_setup(h, d, block.used));
+  // A lane's workspace grows as the single one did, sized by the largest launch the lane has seen; the second lane's is made by
+  // the context's first launch that takes that lane.  While one that is in use is replaced nothing runs on either lane (the
+  // launch is then the first of a new queue, on lane 0; the workspace it was headed for has grown all the same, for the next).
+  const size_t feat_bytes = AlignWorkspace(n_feat_total).bytes;
+  const bool ws_small[2] = { aq.d_feat.ptr && feat_bytes > aq.d_feat.cap, aq.d_feat_lane1.ptr && feat_bytes > aq.d_feat_lane1.cap };
+  plan = place_launch(aq.q, lane_kind, side_kind, ws_small, aq.lane_stream && aq.q.lane1_launches);
+  if (plan.drain_first) {
+    SVOH_ALIGN_DRAIN(ctx);
+    SVOH_HIP_TRY(ctx, aq.workspace(plan.grow_lane).reserve(feat_bytes));
   }
   // (the last wait for the stream of this call lies behind: what follows is this launch's place in the queue)
-  const bool overlapped = lane_kind && ctx->align_chain && ctx->align_launches_since_drain >= 1;   // runs beside the launch before it
-  const int lane = overlapped ? (ctx->align_last_lane ^ 1) : 0;
-  DevBuffer& d_feat = lane ? ctx->d_feat_lane1 : ctx->d_feat;
-  SVOH_HIP_TRY(ctx, d_feat.reserve(feat_bytes));
-  const hipStream_t prev_stream = ctx->align_stream_of(ctx->align_last_lane);   // where the launch before this one runs
-  if (lane) {
-    // whatever was on the context's stream before the queue began stays in front of the second lane as well
-    if (ctx->align_lane1_wants_front) {
-      SVOH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->align_lane_stream, ctx->ev_align_front, 0));
-      ctx->align_lane1_wants_front = false;
-    }
-  } else if (!overlapped) {
-    // the context's stream waits for the second lane, as in every other entry that puts work on it
-    SVOH_ALIGN_JOIN(ctx);
-    if (lane_kind) {   // the launch behind this one may take the second lane: what is on the stream now lies in front of that one too
-      SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_front, ctx->stream));
-      ctx->align_lane1_wants_front = true;
-    }
+  SVOH_HIP_TRY(ctx, aq.workspace(plan.lane).reserve(feat_bytes));
+  ks = aq.stream_of(plan.lane);
+  const hipStream_t prev_stream = aq.stream_of(aq.q.last_lane);   // where the launch before this one runs
+  // whatever was on the context's stream before the queue began stays in front of the second lane as well
+  if (plan.wait_front) {
+    SVOH_HIP_TRY(ctx, hipStreamWaitEvent(aq.lane_stream, aq.ev_front, 0));
+    note_front_waited(aq.q);
   }
-  const hipStream_t ks = ctx->align_stream_of(lane);
-  const bool side = side_kind && ctx->align_launches_since_drain >= 1;
-  const unsigned prev_slot = desc_slot ^ 1u;
-  if (side) {
-    // what this launch does not read must not wait behind it: the launch before this one, if it kept to the context's stream,
+  // the first of a queue: the context's stream waits for the second lane, as in every other entry that puts work on it; the launch
+  // behind this one may take the second lane, and what is on the stream now lies in front of that one too
+  if (plan.join) SVOH_ALIGN_JOIN(ctx);
+  if (plan.record_front) {
+    SVOH_HIP_TRY(ctx, hipEventRecord(aq.ev_front, aq.main));
+    note_front_recorded(aq.q);
+  }
+  if (plan.side) {
+    // what this launch does not read must not wait behind it: the launch before this one, if it kept to its lane,
     // has no event behind its kernel yet (the launch after this one will upload into its block)
-    if (!ctx->align_block_read_ev[prev_slot]) {
-      SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_kernel[prev_slot], prev_stream));
-      ctx->align_block_read_ev[prev_slot] = ctx->ev_align_kernel[prev_slot];
-    }
+    if (plan.record_prev_kernel) SVOH_HIP_TRY(ctx, hipEventRecord(aq.ev_kernel[slot ^ 1u], prev_stream));
     // the kernel of the launch before the last one may still read this device block
-    if (ctx->align_block_read_ev[desc_slot]) SVOH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->align_copy_stream, ctx->align_block_read_ev[desc_slot], 0));
-    SVOH_HIP_TRY(ctx, hipMemcpyAsync(d_desc.ptr, h_desc.ptr, up_base + up_off, hipMemcpyHostToDevice, ctx->align_copy_stream));
-    SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_uploaded, ctx->align_copy_stream));
+    if (plan.wait_block_read) SVOH_HIP_TRY(ctx, hipStreamWaitEvent(aq.copy_stream, aq.ev_kernel[slot], 0));
+    SVOH_HIP_TRY(ctx, hipMemcpyAsync(d, h, block.used, hipMemcpyHostToDevice, aq.copy_stream));
+    SVOH_HIP_TRY(ctx, hipEventRecord(aq.ev_uploaded, aq.copy_stream));
     // what the host waits for before it writes the OTHER pinned block again lies behind the upload that last read that block,
     // the previous launch's: on the copy stream if it went there, else behind that launch's kernel on its lane
-    if (ctx->align_last_was_side) {
-      SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_staged, ctx->align_copy_stream));
-      ctx->align_staged_wait_ev = ctx->ev_align_staged;
-    } else {
-      ctx->align_staged_wait_ev = ctx->align_block_read_ev[prev_slot];
-    }
-    SVOH_HIP_TRY(ctx, align_flush_download(ctx));   // the previous launch's results: behind this upload, beside this kernel
-    SVOH_HIP_TRY(ctx, hipStreamWaitEvent(ks, ctx->ev_align_uploaded, 0));
-    ++ctx->align_side_launches;
+    if (plan.record_staged_on_copy) SVOH_HIP_TRY(ctx, hipEventRecord(aq.ev_staged, aq.copy_stream));
+    SVOH_HIP_TRY(ctx, aq.flush_download());   // the previous launch's results: behind this upload, beside this kernel
+    SVOH_HIP_TRY(ctx, hipStreamWaitEvent(ks, aq.ev_uploaded, 0));
   } else {
-    SVOH_HIP_TRY(ctx, align_flush_download(ctx));
+    SVOH_HIP_TRY(ctx, aq.flush_download());
     // An overlapped launch that keeps its copies on its lane: the launch before it runs on the other lane, so nothing on this
     // lane says that its upload has read the other pinned block.  What the host waits for before it writes that block again
     // (and before the launch after this one uploads into that launch's device block, in-stream or on the copy stream) is
     // recorded behind that launch's kernel instead.
-    if (overlapped) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_staged, prev_stream));
-    SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d_desc.ptr, h_desc.ptr, up_base + up_off, ks));
+    if (plan.record_staged_behind_prev) SVOH_HIP_TRY(ctx, hipEventRecord(aq.ev_staged, prev_stream));
+    SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d, h, block.used, ks));
   }
   if (pos_jobs_device) {
     const int rcp = svoh_launch_pos_from_seed_batch(ctx, (int)pos_jobs.size(), pos_jobs_max_n, pos_jobs_device);
     if (rcp != SVOH_OK) return rcp;
   }
-  ctx->align_desc_slot = desc_slot;
-  if (!side) {
-    ctx->align_staged_wait_ev = nullptr;
-    if (ctx->align_launches_since_drain >= 1) {   // queued behind a launch nobody has waited for: the next one may need this
-      if (!overlapped) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_staged, ks));   // (overlapped: recorded above, behind the previous kernel)
-      ctx->align_staged_wait_ev = ctx->ev_align_staged;
-    }
-    ctx->align_block_read_ev[desc_slot] = nullptr;   // (an event of an earlier kernel on this block says nothing about this one)
-  }
-  ctx->align_last_was_side = side;
-  ++ctx->align_launches_since_drain;
-  ctx->align_last_lane = lane;
-  ctx->align_chain = lane_kind;   // (a launch of another kind on the context's stream ends the queue like any other work there)
-  if (lane) ++ctx->align_lane1_launches;
+  // queued behind a launch nobody has waited for, copies on its lane: the next launch may need to know that the upload has run
+  if (plan.record_staged_behind_upload) SVOH_HIP_TRY(ctx, hipEventRecord(aq.ev_staged, ks));
+  aq.q = commit_launch(aq.q, plan, lane_kind);   // the upload has been queued: the slot is taken
+  return SVOH_OK;
+}
 
-  AlignKernelArgs args;
-  args.problems = static_cast<const DevProblemDesc*>(d_desc.ptr);
-  args.cams = reinterpret_cast<const DevCamDesc*>(args.problems + n_desc);
-  args.results = static_cast<svoh_align_result*>(ctx->d_results.ptr) + dev_results_off;
-  double* w = static_cast<double*>(d_feat.ptr);
-  args.wpk = w;
-  args.slots = (int64_t)feat_slots;
-  args.wsel = reinterpret_cast<uint8_t*>(w + 2 * kWsPairs * feat_slots);
-  args.wvis = args.wsel + feat_slots;
-  args.opt = *opt;
-  args.eval_level = eval_level;
-  args.eval_out = static_cast<double*>(ctx->d_eval.ptr);
-  args.stamps = nullptr;
-  args.n_problems = n_desc;
-  args.ext_state = nullptr;
-  args.raw_sums = 0;
-  args.cluster = 0;
-  args.xchg = nullptr;
-  args.bar = nullptr;
+void AlignCall::arguments()
+{
+  AlignQueue& aq = ctx->aq;
+  base_kernel_args(args, ctx, block, aq.d_desc[slot].ptr, n_desc, AlignWorkspace(n_feat_total), aq.workspace(plan.lane).ptr,
+                   static_cast<svoh_align_result*>(aq.d_results.ptr) + dev_results_off, opt, eval_level);
 #ifdef SVOH_TEST_HOOKS
   args.cluster_test_absent = SvohKnobs::or_default(ctx->knobs.align_cluster_test_absent, 0);
 #endif
-  if (cluster) {
-    const size_t xchg_bytes = 2 * (size_t)S * kXchgStride * sizeof(double) * n_problems;
-    SVOH_HIP_TRY(ctx, ctx->d_xchg.reserve(xchg_bytes));
-    args.cluster = S;
-    args.xchg = static_cast<double*>(ctx->d_xchg.ptr);
-    args.bar = reinterpret_cast<unsigned int*>(static_cast<uint8_t*>(d_desc.ptr) + ctl_off + 256);   // zero, as above
-  }
   if (split && !split->update) {
     args.ext_state = split->ext_state;
     if (S == 1) args.eval_out = split->sums_out;
     args.raw_sums = 1;
   }
-  if (split && split->update) {
-    // the serial step only: one lane, no feature work
-    const bool illum_u = opt->estimate_illumination_gain || opt->estimate_illumination_offset;
-    if (opt->patch_size == 4) {
-      if (illum_u) hipLaunchKernelGGL((align_gn_update_kernel<4, true>), dim3(1), dim3(64), 0, ctx->stream, args, split->sums_in, split->state, eval_level, split->iter);
-      else hipLaunchKernelGGL((align_gn_update_kernel<4, false>), dim3(1), dim3(64), 0, ctx->stream, args, split->sums_in, split->state, eval_level, split->iter);
-    } else {
-      if (illum_u) hipLaunchKernelGGL((align_gn_update_kernel<8, true>), dim3(1), dim3(64), 0, ctx->stream, args, split->sums_in, split->state, eval_level, split->iter);
-      else hipLaunchKernelGGL((align_gn_update_kernel<8, false>), dim3(1), dim3(64), 0, ctx->stream, args, split->sums_in, split->state, eval_level, split->iter);
-    }
-    const hipError_t eu = hipGetLastError();
-    if (eu != hipSuccess) return set_error(ctx, SVOH_ERR_HIP, "gn_update launch failed: %s", hipGetErrorString(eu));
-    return SVOH_OK;
+}
+
+// patch-split mode, the serial step only: one lane, no feature work
+int AlignCall::launch_update()
+{
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(1), dim3(64), 0, ctx->stream, args, split->sums_in, split->state, eval_level, split->iter);
+    return hipGetLastError();
+  };
+  const bool illum_u = opt->estimate_illumination_gain || opt->estimate_illumination_offset;
+  const hipError_t eu = opt->patch_size == 4 ? (illum_u ? go(align_gn_update_kernel<4, true>) : go(align_gn_update_kernel<4, false>))
+                                             : (illum_u ? go(align_gn_update_kernel<8, true>) : go(align_gn_update_kernel<8, false>));
+  if (eu != hipSuccess) return set_error(ctx, SVOH_ERR_HIP, "gn_update launch failed: %s", hipGetErrorString(eu));
+  return SVOH_OK;
+}
+
+// the geometry's LDS and grid, the kernel, and what the context remembers of the launch
+int AlignCall::launch()
+{
+  AlignQueue& aq = ctx->aq;
+  if (cluster) {
+    const size_t xchg_bytes = 2 * (size_t)S * kXchgStride * sizeof(double) * n_problems;
+    SVOH_HIP_TRY(ctx, ctx->d_xchg.reserve(xchg_bytes));
+    args.cluster = S;
+    args.xchg = static_cast<double*>(ctx->d_xchg.ptr);
+    args.bar = reinterpret_cast<unsigned int*>(static_cast<uint8_t*>(aq.d_desc[slot].ptr) + block.bar_off);   // zero, as the queue head
   }
-  args.queue = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(d_desc.ptr) + ctl_off);   // zero: uploaded with the descriptors
 #ifdef SVOH_PHASE_STAMPS
   SVOH_HIP_TRY(ctx, ctx->d_scratch0.reserve(sizeof(long long) * 20 * (size_t)n_problems));
   args.stamps = static_cast<long long*>(ctx->d_scratch0.ptr);
@@ -2366,10 +2427,8 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   if (lds > lds_cap) lds = lds_cap;
   // a small problem's feature workspace in LDS, behind the image area (512-thread geometry: 78 KB hold the 50 KB of the
   // levels 4..2 of a 640x480 pair and 16 KB of rows; the next finer level would not fit either way)
-  args.ws_lds_bytes = 0;
-  if (nt == 512 && !cluster && max_feat_per_problem <= kWsLdsMaxFeatures && lds >= (size_t)kWsLdsMaxFeatures * kWsPairs * 16 + 4096) {
-    args.ws_lds_bytes = ((max_feat_per_problem > 0 ? max_feat_per_problem : 1) * kWsPairs * 16 + 15) & ~15;
-  }
+  if (nt == 512 && !cluster && shape.max_feat_per_problem <= kWsLdsMaxFeatures && lds >= (size_t)kWsLdsMaxFeatures * kWsPairs * 16 + 4096)
+    args.ws_lds_bytes = ws_lds_bytes_for(shape.max_feat_per_problem);
   args.lds_img_bytes = (int32_t)(lds - (size_t)args.ws_lds_bytes);   // the launch still asks for all of `lds`
 
   const bool illum = opt->estimate_illumination_gain || opt->estimate_illumination_offset;
@@ -2377,11 +2436,10 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   int grid = ctx->num_cus * SvohKnobs::or_default(ctx->knobs.align_wg_per_cu, nt == 256 ? 2 : nt == 128 ? 4 : 1);
   if (grid > n_desc || grid <= 0) grid = n_desc;
   if (cluster) grid = n_desc;
-  args.one_each = 0;   // (not read: see AlignKernelArgs)
   hipError_t e;
   const bool timed = ctx->timing_on();
-  const int ev_slot = (int)(ctx->align_timed_launches % svoh_ctx::kAlignEventRing);
-  if (timed) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_start[ev_slot], ks));
+  const int ev_slot = (int)(aq.timed_launches % AlignQueue::kEventRing);
+  if (timed) SVOH_HIP_TRY(ctx, hipEventRecord(aq.ev_start[ev_slot], ks));
   const bool robust = opt->robustification != 0;
   int32_t lds_img_launched = 0;
 #ifdef SVOH_DEV_ONLY_PLAIN   // development builds only (scripts/kernel_resources.sh, quick A/B libraries): the 4x4 / 8x8 kernels without illumination terms and robust weights
@@ -2400,49 +2458,55 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
   if (e != hipSuccess)
     return set_error(ctx, SVOH_ERR_HIP, "sparse_align launch failed: %s", hipGetErrorString(e));
   if (S > 1 && !cluster) {
-    hipLaunchKernelGGL(sum_shares_kernel, dim3(1), dim3(128), 0, ctx->stream, static_cast<const double*>(ctx->d_eval.ptr), S,
+    hipLaunchKernelGGL(sum_shares_kernel, dim3(1), dim3(128), 0, ctx->stream, static_cast<const double*>(aq.d_eval.ptr), S,
                        split->sums_out);
     const hipError_t es = hipGetLastError();
     if (es != hipSuccess) return set_error(ctx, SVOH_ERR_HIP, "sum_shares launch failed: %s", hipGetErrorString(es));
   }
-  if (timed) { SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_stop[ev_slot], ks)); ++ctx->align_timed_launches; }
-  ctx->align_last_timed = timed;
-  ++ctx->align_launches;
+  if (timed) { SVOH_HIP_TRY(ctx, hipEventRecord(aq.ev_stop[ev_slot], ks)); ++aq.timed_launches; }
+  aq.last_timed = timed;
+  ++aq.launches;
   if (!split && eval_level < 0) {   // svoh_sparse_align_last_launch_info
-    ctx->align_last_geometry_key = geo.key(); ctx->align_last_grid = grid; ctx->align_last_n_desc = n_desc;
-    ctx->align_last_lds_img_bytes = lds_img_launched;
+    aq.last_geometry_key = geo.key(); aq.last_grid = grid; aq.last_n_desc = n_desc;
+    aq.last_lds_img_bytes = lds_img_launched;
   }
-  ctx->align_last_info_lane = lane;   // svoh_sparse_align_last_launch_lane: of every launch, evaluations included
-  // the results follow the kernel to pinned host memory right away, so that a caller which queues several
-  // launches and fetches once still has every launch's output delivered
-  if (side) {
+  aq.last_info_lane = plan.lane;   // svoh_sparse_align_last_launch_lane: of every launch, evaluations included
+  return SVOH_OK;
+}
+
+// The results follow the kernel to pinned host memory right away, so that a caller which queues several launches and fetches
+// once still has every launch's output delivered; the events the launches behind this one will wait for.
+int AlignCall::deliver()
+{
+  AlignQueue& aq = ctx->aq;
+  svoh_align_result* const h_dst = static_cast<svoh_align_result*>(aq.h_results.ptr) + aq.pending_results;
+  if (plan.record_kernel) {
     // behind this kernel: the copy stream may write this device block again (the launch after the next), and take the results
-    SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_kernel[desc_slot], ks));
-    ctx->align_block_read_ev[desc_slot] = ctx->ev_align_kernel[desc_slot];
-    // held back until the next launch has queued its upload, or somebody drains (align_flush_download)
-    ctx->align_download.dst = static_cast<svoh_align_result*>(ctx->h_results.ptr) + ctx->align_pending_results;
-    ctx->align_download.src = args.results;
-    ctx->align_download.bytes = sizeof(svoh_align_result) * n_problems;
-    ctx->align_download.after = ctx->ev_align_kernel[desc_slot];
+    SVOH_HIP_TRY(ctx, hipEventRecord(aq.ev_kernel[slot], ks));
+    note_kernel_recorded(aq.q, plan);
+    // held back until the next launch has queued its upload, or somebody drains (flush_download)
+    aq.download.dst = h_dst;
+    aq.download.src = args.results;
+    aq.download.bytes = sizeof(svoh_align_result) * n_problems;
+    aq.download.after = aq.ev_kernel[slot];
   }
   if (delivers) {   // cluster: entry 0 is share 0's copy of the common result
-    if (!side)
-      SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, static_cast<svoh_align_result*>(ctx->h_results.ptr) + ctx->align_pending_results,
-                                          args.results, sizeof(svoh_align_result) * n_problems, ks));
-    ctx->align_last_results_off = ctx->align_pending_results;
+    if (!plan.side) SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, h_dst, args.results, sizeof(svoh_align_result) * n_problems, ks));
+    aq.last_results_off = aq.pending_results;
     // where on the device result #k of the queue lives (svoh_project_candidates_enqueue's align_result_index)
-    if (ctx->align_pending_results == 0) ctx->align_result_dev_index.clear();
-    for (int p = 0; p < n_problems; ++p) ctx->align_result_dev_index.push_back((uint32_t)(dev_results_off + (size_t)p));
-    ctx->align_pending_results += (size_t)n_problems;
-    ctx->align_pending_dev = dev_results_off + (size_t)n_desc + (size_t)n_problems;
+    if (aq.pending_results == 0) aq.result_dev_index.clear();
+    for (int p = 0; p < n_problems; ++p) aq.result_dev_index.push_back((uint32_t)(dev_results_off + (size_t)p));
+    aq.pending_results += (size_t)n_problems;
+    aq.pending_dev = dev_results_off + (size_t)n_desc + (size_t)n_problems;
   }
   // the second lane's launch is what the context's stream has to wait for before anything else uses its results or its inputs
-  if (lane) {
-    SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_lane1, ks));
-    ctx->align_lane1_pending = true;
+  if (plan.record_lane1) {
+    SVOH_HIP_TRY(ctx, hipEventRecord(aq.ev_lane1, ks));
+    note_lane1_recorded(aq.q);
   }
 #ifdef SVOH_PHASE_STAMPS
   {
+    const int nt = geo.nt;
     std::vector<long long> h((size_t)n_problems * 20);
     SVOH_HIP_TRY(ctx, hipMemcpyAsync(h.data(), args.stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost, ks));
     SVOH_ALIGN_DRAIN(ctx);
@@ -2460,8 +2524,26 @@ static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_pro
 #endif
   // what svoh_sparse_align_fetch may hand out: only a launch that delivered into h_results (not an evaluation, not
   // the shares of a patch-split evaluation, whose result slots are not a caller's problems)
-  ctx->last_align_n = delivers ? n_problems : 0;
+  aq.last_n = delivers ? n_problems : 0;
   return SVOH_OK;
+}
+
+// Build descriptors, upload host feature arrays if needed, launch.
+static int enqueue_align(svoh_ctx* ctx, const svoh_align_options* opt, int n_problems,
+                         const svoh_align_problem* problems, int eval_level, const SplitArgs* split = nullptr,
+                         const AlignGeometry* forced = nullptr)
+{
+  if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
+  AlignCall call(ctx, opt, n_problems, problems, eval_level, split, forced);
+  int rc = call.size();                                // checks and sizes
+  if (rc == SVOH_OK) rc = call.take_blocks();          // its descriptor slot; room in the blocks and the result queues
+  if (rc == SVOH_OK) rc = call.fill();                 // descriptors and host arrays into the pinned block
+  if (rc == SVOH_OK) rc = call.place_and_upload();     // its place in the queue; the upload
+  if (rc != SVOH_OK) return rc;
+  call.arguments();
+  if (call.update()) return call.launch_update();
+  rc = call.launch();
+  return rc == SVOH_OK ? call.deliver() : rc;
 }
 
 // ---- the wide camera family: svoh_sparse_align_wide_batch / _wide_evaluate ------------------------------------------------------
@@ -2486,7 +2568,7 @@ static int check_wide_call(svoh_ctx* ctx, const svoh_align_options* opt, int n_p
   const int rc = validate_options(ctx, opt);
   if (rc != SVOH_OK) return rc;
   SVOH_REQUIRE(ctx, n_problems >= 1 && problems, "no problems");
-  SVOH_REQUIRE(ctx, ctx->align_pending_results == 0,
+  SVOH_REQUIRE(ctx, ctx->aq.pending_results == 0,
                "the wide alignment entries are blocking: fetch the results of earlier svoh_sparse_align_enqueue calls first");
   SVOH_REQUIRE(ctx, !ctx->matcher_deferred, "the wide alignment entries cannot be called inside a deferred matcher section");
   *any_wide = false;
@@ -2519,13 +2601,16 @@ static int check_wide_call(svoh_ctx* ctx, const svoh_align_options* opt, int n_p
 // the evaluation's outputs where svoh_sparse_align_evaluate's are (d_eval, the byte masks behind d_feat's rows).  Nothing is in
 // flight when it starts (no results are queued; both lanes are drained) and nothing when it returns, so it uses the alignment's
 // blocks of slot 0 without touching the queue's bookkeeping; svoh_sparse_align_last_launch_info / _lds / _lane are left alone.
+// The block is enqueue_align's with one share per problem and every camera's arrays uploaded.
 static int run_align_wide(svoh_ctx* ctx, const svoh_align_options* opt, int n_problems, const svoh_align_problem* problems, int eval_level)
 {
+  AlignQueue& aq = ctx->aq;
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   // pass 1: sizes, and every check that can fail -- before a byte is staged
-  size_t n_cams_total = 0, n_feat_total = 0, host_bytes = 0;
+  size_t n_cams_total = 0, n_feat_total = 0;
   int max_feat_per_problem = 0;
   const int need_levels = opt->max_level + 1;
+  AlignBlock block;
   for (int p = 0; p < n_problems; ++p) {
     const svoh_align_problem& pb = problems[p];
     int64_t nf = 0;
@@ -2533,129 +2618,76 @@ static int run_align_wide(svoh_ctx* ctx, const svoh_align_options* opt, int n_pr
       const svoh_align_camera& cam = pb.cams[c];
       SVOH_REQUIRE(ctx, cam.n_features >= 0, "negative n_features");
       SVOH_REQUIRE(ctx, cam.n_features == 0 || (cam.px && cam.f && cam.pos_world && cam.flags), "NULL feature array");
-      const Frame* fr = find_frame(ctx, cam.ref_frame);
-      const Frame* fc = find_frame(ctx, cam.cur_frame);
-      if (!fr || !fc) return set_error(ctx, SVOH_ERR_BAD_HANDLE, "problem %d camera %d: unknown frame handle", p, c);
-      if (fr->n_levels < need_levels || fc->n_levels < need_levels)
-        return set_error(ctx, SVOH_ERR_INVALID_ARGUMENT, "problem %d camera %d: pyramid has fewer than %d levels", p, c, need_levels);
-      const double dev = ref_extrinsics_deviation(cam);
-      if (!(dev <= 1e-9))
-        return set_error(ctx, SVOH_ERR_INVALID_ARGUMENT,
-                         "problem %d camera %d: ref_T_cam_imu is not the inverse of ref_T_imu_cam (deviation %.3g)", p, c, dev);
+      const Frame *fr, *fc;
+      const int rc = check_align_camera(ctx, cam, p, c, need_levels, &fr, &fc);
+      if (rc != SVOH_OK) return rc;
       nf += cam.n_features;
-      host_bytes += ((size_t)cam.n_features * 65 + 63) & ~(size_t)63;
+      block.size_camera((size_t)cam.n_features);
     }
     SVOH_REQUIRE(ctx, nf <= INT32_MAX && n_feat_total + (size_t)nf <= (size_t)INT32_MAX, "too many features in one launch");
     n_cams_total += (size_t)pb.n_cams;
     n_feat_total += (size_t)nf;
     if ((int)nf > max_feat_per_problem) max_feat_per_problem = (int)nf;
   }
-  const size_t feat_slots = n_feat_total ? n_feat_total : 1;
+  block.lay_out((size_t)n_problems, n_cams_total, sizeof(DevProblemDesc), sizeof(DevCamDesc));
+  const AlignWorkspace ws(n_feat_total);
   SVOH_ALIGN_JOIN(ctx);
   SVOH_ALIGN_DRAIN(ctx);
 
-  // the block of enqueue_align: descriptors, the zeroed queue head (256-byte aligned), the cameras' arrays
-  const size_t desc_only = sizeof(DevProblemDesc) * (size_t)n_problems + sizeof(DevCamDesc) * n_cams_total;
-  const size_t ctl_off = (desc_only + 255) & ~(size_t)255;
-  const size_t up_base = ctl_off + 512;
-  const size_t desc_bytes = up_base + host_bytes;
-  PinnedBuffer& h_desc = ctx->h_desc;
-  DevBuffer& d_desc = ctx->d_desc[0];
-  SVOH_HIP_TRY(ctx, h_desc.reserve(desc_bytes));
-  SVOH_HIP_TRY(ctx, d_desc.reserve(desc_bytes));
-  SVOH_HIP_TRY(ctx, ctx->d_results.reserve(sizeof(svoh_align_result) * (size_t)n_problems));
-  SVOH_HIP_TRY(ctx, ctx->h_results.reserve(sizeof(svoh_align_result) * (size_t)n_problems));
-  SVOH_HIP_TRY(ctx, ctx->d_eval.reserve(74 * sizeof(double) * (size_t)n_problems));
-  SVOH_HIP_TRY(ctx, ctx->d_feat.reserve(feat_slots * (kWsPairs * 16 + 2) + 256));
-  memset(static_cast<uint8_t*>(h_desc.ptr) + ctl_off, 0, 512);
+  PinnedBuffer& h_desc = aq.h_block(0);
+  DevBuffer& d_desc = aq.d_desc[0];
+  SVOH_HIP_TRY(ctx, h_desc.reserve(block.reserve));
+  SVOH_HIP_TRY(ctx, d_desc.reserve(block.reserve));
+  SVOH_HIP_TRY(ctx, aq.d_results.reserve(sizeof(svoh_align_result) * (size_t)n_problems));
+  SVOH_HIP_TRY(ctx, aq.h_results.reserve(sizeof(svoh_align_result) * (size_t)n_problems));
+  SVOH_HIP_TRY(ctx, aq.d_eval.reserve(74 * sizeof(double) * (size_t)n_problems));
+  SVOH_HIP_TRY(ctx, aq.d_feat.reserve(ws.bytes));
+  uint8_t* const h = static_cast<uint8_t*>(h_desc.ptr);
+  const uint8_t* const d = static_cast<const uint8_t*>(d_desc.ptr);
+  memset(h + block.ctl_off, 0, kAlignCtlBytes);
 
-  DevProblemDesc* hp = static_cast<DevProblemDesc*>(h_desc.ptr);
-  DevCamDesc* hc = reinterpret_cast<DevCamDesc*>(hp + n_problems);
-  uint8_t* hup = static_cast<uint8_t*>(h_desc.ptr) + up_base;
-  const uint8_t* dup = static_cast<const uint8_t*>(d_desc.ptr) + up_base;
-  size_t up_off = 0;
+  DevProblemDesc* hp = reinterpret_cast<DevProblemDesc*>(h);
+  DevCamDesc* hc = reinterpret_cast<DevCamDesc*>(h + block.cams_off);
   int cam_idx = 0, feat_off = 0;
   for (int p = 0; p < n_problems; ++p) {
     const svoh_align_problem& pb = problems[p];
-    DevProblemDesc& d = hp[p];
-    d.n_cams = pb.n_cams;
-    d.cam_begin = cam_idx;
-    d.T_init = pb.T_icur_iref;
-    d.alpha_init = pb.alpha_init; d.beta_init = pb.beta_init;
-    d.prior = pb.prior;
+    fill_problem_desc(hp[p], pb, cam_idx);
     for (int c = 0; c < pb.n_cams; ++c, ++cam_idx) {
       const svoh_align_camera& cam = pb.cams[c];
-      DevCamDesc& dc = hc[cam_idx];
-      const Frame* fr = find_frame(ctx, cam.ref_frame);
-      const Frame* fc = find_frame(ctx, cam.cur_frame);
-      for (int l = 0; l < SVOH_MAX_LEVELS; ++l) {
-        dc.ref[l] = l < fr->n_levels ? fr->lv[l] : DevImage{ nullptr, 0, 0, 0, 0 };
-        dc.cur[l] = l < fc->n_levels ? fc->lv[l] : DevImage{ nullptr, 0, 0, 0, 0 };
-      }
-      dc.cam = cam.cam;
-      dc.ref_T_imu_cam = cam.ref_T_imu_cam;
-      dc.ref_T_cam_imu = cam.ref_T_cam_imu;
-      dc.cur_T_cam_imu = cam.cur_T_cam_imu;
-      for (int k = 0; k < 3; ++k) dc.ref_pos[k] = cam.ref_pos[k];
-      dc.n_features = cam.n_features;
-      dc.feat_off = feat_off;
-      feat_off += cam.n_features;
       const size_t n = (size_t)cam.n_features;
-      uint8_t* h = hup + up_off;
-      if (n) {
-        memcpy(h, cam.px, n * 16);
-        memcpy(h + n * 16, cam.f, n * 24);
-        memcpy(h + n * 40, cam.pos_world, n * 24);
-        memcpy(h + n * 64, cam.flags, n);
-      }
-      const uint8_t* dv = dup + up_off;
-      dc.px = reinterpret_cast<const double*>(dv);
-      dc.f = reinterpret_cast<const double*>(dv + n * 16);
-      dc.pos_world = reinterpret_cast<const double*>(dv + n * 40);
-      dc.flags = dv + n * 64;
-      up_off += (n * 65 + 63) & ~(size_t)63;
+      const size_t at = block.place_camera(n);
+      gather_camera(h + at, cam, n);
+      fill_cam_desc(hc[cam_idx], cam, *find_frame(ctx, cam.ref_frame), *find_frame(ctx, cam.cur_frame), uploaded_columns(d + at, n),
+                    AlignShare(cam.n_features, 0, 1), feat_off);
+      feat_off += cam.n_features;
     }
   }
-  SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d_desc.ptr, h_desc.ptr, up_base + up_off));
+  SVOH_HIP_TRY(ctx, svoh_copy_to_device(ctx, d_desc.ptr, h_desc.ptr, block.used));
 
   AlignKernelArgs args;
-  memset(&args, 0, sizeof args);
-  args.problems = static_cast<const DevProblemDesc*>(d_desc.ptr);
-  args.cams = reinterpret_cast<const DevCamDesc*>(args.problems + n_problems);
-  args.results = static_cast<svoh_align_result*>(ctx->d_results.ptr);
-  double* w = static_cast<double*>(ctx->d_feat.ptr);
-  args.wpk = w;
-  args.slots = (int64_t)feat_slots;
-  args.wsel = reinterpret_cast<uint8_t*>(w + 2 * kWsPairs * feat_slots);
-  args.wvis = args.wsel + feat_slots;
-  args.opt = *opt;
-  args.eval_level = eval_level;
-  args.eval_out = static_cast<double*>(ctx->d_eval.ptr);
-  args.n_problems = n_problems;
-  args.queue = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(d_desc.ptr) + ctl_off);   // zero: uploaded with the descriptors
+  base_kernel_args(args, ctx, block, d_desc.ptr, n_problems, ws, aq.d_feat.ptr, static_cast<svoh_align_result*>(aq.d_results.ptr), opt, eval_level);
 #ifdef SVOH_PHASE_STAMPS
   SVOH_HIP_TRY(ctx, ctx->d_scratch0.reserve(sizeof(long long) * 20 * (size_t)n_problems));
   args.stamps = static_cast<long long*>(ctx->d_scratch0.ptr);
 #endif
   // the 512-thread geometry's LDS: 78 KB, the rows of a small problem behind the image area (enqueue_align)
   const size_t lds = 78 * 1024;
-  if (max_feat_per_problem <= kWsLdsMaxFeatures)
-    args.ws_lds_bytes = ((max_feat_per_problem > 0 ? max_feat_per_problem : 1) * kWsPairs * 16 + 15) & ~15;
+  if (max_feat_per_problem <= kWsLdsMaxFeatures) args.ws_lds_bytes = ws_lds_bytes_for(max_feat_per_problem);
   args.lds_img_bytes = (int32_t)(lds - (size_t)args.ws_lds_bytes);
   const int grid = n_problems < ctx->num_cus ? n_problems : ctx->num_cus;   // persistent workgroups, one per compute unit
   const bool illum = opt->estimate_illumination_gain || opt->estimate_illumination_offset;
   const bool robust = opt->robustification != 0;
   const bool timed = ctx->timing_on();
-  const int ev_slot = (int)(ctx->align_timed_launches % svoh_ctx::kAlignEventRing);
-  if (timed) SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_start[ev_slot], ctx->stream));
+  const int ev_slot = (int)(aq.timed_launches % AlignQueue::kEventRing);
+  if (timed) SVOH_HIP_TRY(ctx, hipEventRecord(aq.ev_start[ev_slot], ctx->stream));
   const hipError_t e = opt->patch_size == 4 ? launch_wide<4>(ctx->stream, illum, robust, grid, lds, args)
                                             : launch_wide<8>(ctx->stream, illum, robust, grid, lds, args);
   if (e != hipSuccess) return set_error(ctx, SVOH_ERR_HIP, "sparse_align_wide launch failed: %s", hipGetErrorString(e));
-  if (timed) { SVOH_HIP_TRY(ctx, hipEventRecord(ctx->ev_align_stop[ev_slot], ctx->stream)); ++ctx->align_timed_launches; }
-  ctx->align_last_timed = timed;
+  if (timed) { SVOH_HIP_TRY(ctx, hipEventRecord(aq.ev_stop[ev_slot], ctx->stream)); ++aq.timed_launches; }
+  aq.last_timed = timed;
   if (eval_level < 0)
-    SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, ctx->h_results.ptr, args.results, sizeof(svoh_align_result) * (size_t)n_problems));
-  ctx->last_align_n = 0;   // nothing for svoh_sparse_align_fetch: the caller of this function hands the results out
+    SVOH_HIP_TRY(ctx, svoh_copy_to_host(ctx, aq.h_results.ptr, args.results, sizeof(svoh_align_result) * (size_t)n_problems));
+  aq.last_n = 0;   // nothing for svoh_sparse_align_fetch: the caller of this function hands the results out
   return SVOH_OK;
 }
 
@@ -2663,17 +2695,17 @@ static int run_align_wide(svoh_ctx* ctx, const svoh_align_options* opt, int n_pr
 static int fetch_evaluation(svoh_ctx* ctx, const svoh_align_problem* problem, double* H64, double* g8, double* chi2, int32_t* n_meas,
                             uint8_t* visibility, int32_t* n_selected)
 {
+  AlignQueue& aq = ctx->aq;
   double out[74];
-  SVOH_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_eval.ptr, sizeof out, hipMemcpyDeviceToHost, ctx->stream));
+  SVOH_HIP_TRY(ctx, hipMemcpyAsync(out, aq.d_eval.ptr, sizeof out, hipMemcpyDeviceToHost, ctx->stream));
   int nf = 0;
   for (int c = 0; c < problem->n_cams; ++c) nf += problem->cams[c].n_features;
   std::vector<uint8_t> sel((size_t)nf + 1), vis((size_t)nf + 1);
-  // workspace layout: see enqueue_align
-  const size_t slots = nf ? (size_t)nf : 1;
-  const uint8_t* dsel = reinterpret_cast<const uint8_t*>(static_cast<double*>(ctx->d_feat.ptr) + 2 * kWsPairs * slots);
+  const AlignWorkspace ws((size_t)nf);
+  const uint8_t* w = static_cast<const uint8_t*>(aq.d_feat.ptr);
   if (nf) {
-    SVOH_HIP_TRY(ctx, hipMemcpyAsync(sel.data(), dsel, (size_t)nf, hipMemcpyDeviceToHost, ctx->stream));
-    SVOH_HIP_TRY(ctx, hipMemcpyAsync(vis.data(), dsel + slots, (size_t)nf, hipMemcpyDeviceToHost, ctx->stream));
+    SVOH_HIP_TRY(ctx, hipMemcpyAsync(sel.data(), w + ws.wsel_off, (size_t)nf, hipMemcpyDeviceToHost, ctx->stream));
+    SVOH_HIP_TRY(ctx, hipMemcpyAsync(vis.data(), w + ws.wvis_off, (size_t)nf, hipMemcpyDeviceToHost, ctx->stream));
   }
   SVOH_ALIGN_DRAIN(ctx);
   memcpy(H64, out, 64 * sizeof(double));
@@ -2701,7 +2733,7 @@ try {
 
 #ifdef SVOH_TEST_HOOKS
 // libsvo_hip_testhooks.so only (not part of include/svo_hip.h): how many launches of this context took the side path
-unsigned long long svoh_test_align_side_launches(const svoh_ctx* ctx) { return ctx ? ctx->align_side_launches : 0; }
+unsigned long long svoh_test_align_side_launches(const svoh_ctx* ctx) { return ctx ? ctx->aq.q.side_launches : 0; }
 #endif
 
 int svoh_sparse_align_geometry_key(svoh_ctx* ctx, const svoh_align_options* options, const svoh_align_problem* problem, int32_t* key)
@@ -2721,7 +2753,7 @@ int svoh_set_align_geometry_classes(svoh_ctx* ctx, int shared)
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, shared == 0 || shared == 1, "geometry classes: 0 = the fastest geometry for a problem alone, 1 = shared classes");
-  if (ctx->align_launches_since_drain && ctx->align_lane_stream) SVOH_ALIGN_DRAIN(ctx);   // the geometry of launches is planned anew: both lanes run empty first
+  if (ctx->aq.q.launches_since_drain && ctx->aq.lane_stream) SVOH_ALIGN_DRAIN(ctx);   // the geometry of launches is planned anew: both lanes run empty first
   ctx->align_shared_classes = shared != 0;
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
@@ -2754,27 +2786,27 @@ try {
 int svoh_sparse_align_fetch(svoh_ctx* ctx, int n_problems, svoh_align_result* results)
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  SVOH_REQUIRE(ctx, results && n_problems >= 1 && n_problems <= ctx->last_align_n && ctx->h_results.ptr &&
-                        ctx->align_pending_results >= (size_t)n_problems, "nothing to fetch");
+  SVOH_REQUIRE(ctx, results && n_problems >= 1 && n_problems <= ctx->aq.last_n && ctx->aq.h_results.ptr &&
+                        ctx->aq.pending_results >= (size_t)n_problems, "nothing to fetch");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   SVOH_ALIGN_DRAIN(ctx);   // the copy to h_results was queued behind the kernel
-  memcpy(results, static_cast<const svoh_align_result*>(ctx->h_results.ptr) + ctx->align_last_results_off,
+  memcpy(results, static_cast<const svoh_align_result*>(ctx->aq.h_results.ptr) + ctx->aq.last_results_off,
          sizeof(svoh_align_result) * n_problems);
-  ctx->align_pending_results = 0;
-  ctx->align_pending_dev = 0;
+  ctx->aq.pending_results = 0;
+  ctx->aq.pending_dev = 0;
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
 
 int svoh_sparse_align_fetch_all(svoh_ctx* ctx, int n_results, svoh_align_result* results)
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  SVOH_REQUIRE(ctx, results && n_results >= 1 && (size_t)n_results == ctx->align_pending_results,
+  SVOH_REQUIRE(ctx, results && n_results >= 1 && (size_t)n_results == ctx->aq.pending_results,
                "n_results is not the number of results queued since the last fetch");
   SVOH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   SVOH_ALIGN_DRAIN(ctx);
-  memcpy(results, ctx->h_results.ptr, sizeof(svoh_align_result) * (size_t)n_results);
-  ctx->align_pending_results = 0;
-  ctx->align_pending_dev = 0;
+  memcpy(results, ctx->aq.h_results.ptr, sizeof(svoh_align_result) * (size_t)n_results);
+  ctx->aq.pending_results = 0;
+  ctx->aq.pending_dev = 0;
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
 
@@ -2803,11 +2835,11 @@ try {
 int svoh_sparse_align_last_kernel_ms(svoh_ctx* ctx, float* ms)
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
-  SVOH_REQUIRE(ctx, ms != nullptr && ctx->align_timed_launches > 0 && ctx->align_last_timed,
+  SVOH_REQUIRE(ctx, ms != nullptr && ctx->aq.timed_launches > 0 && ctx->aq.last_timed,
                "the last alignment launch was not timed (svoh_set_kernel_timing)");
-  const int slot = (int)((ctx->align_timed_launches - 1) % svoh_ctx::kAlignEventRing);
-  SVOH_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_align_stop[slot]));
-  SVOH_HIP_TRY(ctx, hipEventElapsedTime(ms, ctx->ev_align_start[slot], ctx->ev_align_stop[slot]));
+  const int slot = (int)((ctx->aq.timed_launches - 1) % AlignQueue::kEventRing);
+  SVOH_HIP_TRY(ctx, hipEventSynchronize(ctx->aq.ev_stop[slot]));
+  SVOH_HIP_TRY(ctx, hipEventElapsedTime(ms, ctx->aq.ev_start[slot], ctx->aq.ev_stop[slot]));
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
 
@@ -2815,8 +2847,8 @@ int svoh_sparse_align_last_launch_info(svoh_ctx* ctx, int32_t* geometry_key, int
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, geometry_key && grid && n_desc, "NULL argument");
-  SVOH_REQUIRE(ctx, ctx->align_last_geometry_key != 0, "no full-run alignment launch on this context yet");
-  *geometry_key = ctx->align_last_geometry_key; *grid = ctx->align_last_grid; *n_desc = ctx->align_last_n_desc;
+  SVOH_REQUIRE(ctx, ctx->aq.last_geometry_key != 0, "no full-run alignment launch on this context yet");
+  *geometry_key = ctx->aq.last_geometry_key; *grid = ctx->aq.last_grid; *n_desc = ctx->aq.last_n_desc;
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
 
@@ -2824,10 +2856,10 @@ int svoh_sparse_align_last_launch_lane(svoh_ctx* ctx, int32_t* lane, int32_t* la
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, lane && lanes, "NULL argument");
-  SVOH_REQUIRE(ctx, ctx->align_launches != 0, "no alignment launch on this context yet");
-  *lane = ctx->align_last_info_lane;
-  *lanes = ctx->align_lane_stream ? 2 : 1;
-  if (lane1_launches) *lane1_launches = ctx->align_lane1_launches;
+  SVOH_REQUIRE(ctx, ctx->aq.launches != 0, "no alignment launch on this context yet");
+  *lane = ctx->aq.last_info_lane;
+  *lanes = ctx->aq.lane_stream ? 2 : 1;
+  if (lane1_launches) *lane1_launches = ctx->aq.q.lane1_launches;
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
 
@@ -2835,8 +2867,8 @@ int svoh_sparse_align_last_launch_lds(svoh_ctx* ctx, int32_t* lds_img_bytes)
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, lds_img_bytes, "NULL argument");
-  SVOH_REQUIRE(ctx, ctx->align_last_geometry_key != 0, "no full-run alignment launch on this context yet");
-  *lds_img_bytes = ctx->align_last_lds_img_bytes;
+  SVOH_REQUIRE(ctx, ctx->aq.last_geometry_key != 0, "no full-run alignment launch on this context yet");
+  *lds_img_bytes = ctx->aq.last_lds_img_bytes;
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
 
@@ -2844,13 +2876,13 @@ int svoh_sparse_align_kernel_ms_history(svoh_ctx* ctx, int n, float* ms, int* n_
 try {
   if (!ctx) return set_error(nullptr, SVOH_ERR_INVALID_ARGUMENT, "ctx is NULL");
   SVOH_REQUIRE(ctx, ms != nullptr && n_out != nullptr && n >= 0, "bad arguments");
-  int have = (int)(ctx->align_timed_launches < (unsigned long long)svoh_ctx::kAlignEventRing ? ctx->align_timed_launches
-                                                                                             : (unsigned long long)svoh_ctx::kAlignEventRing);
+  int have = (int)(ctx->aq.timed_launches < (unsigned long long)AlignQueue::kEventRing ? ctx->aq.timed_launches
+                                                                                             : (unsigned long long)AlignQueue::kEventRing);
   if (n < have) have = n;
   for (int k = 0; k < have; ++k) {   // oldest of the requested launches first
-    const int slot = (int)((ctx->align_timed_launches - (unsigned long long)have + (unsigned long long)k) % svoh_ctx::kAlignEventRing);
-    SVOH_HIP_TRY(ctx, hipEventSynchronize(ctx->ev_align_stop[slot]));
-    SVOH_HIP_TRY(ctx, hipEventElapsedTime(&ms[k], ctx->ev_align_start[slot], ctx->ev_align_stop[slot]));
+    const int slot = (int)((ctx->aq.timed_launches - (unsigned long long)have + (unsigned long long)k) % AlignQueue::kEventRing);
+    SVOH_HIP_TRY(ctx, hipEventSynchronize(ctx->aq.ev_stop[slot]));
+    SVOH_HIP_TRY(ctx, hipEventElapsedTime(&ms[k], ctx->aq.ev_start[slot], ctx->aq.ev_stop[slot]));
   }
   *n_out = have;
   return SVOH_OK;
@@ -2880,7 +2912,7 @@ try {
   rc = run_align_wide(ctx, options, n_problems, problems, -1);
   if (rc != SVOH_OK) return rc;
   SVOH_ALIGN_DRAIN(ctx);
-  memcpy(results, ctx->h_results.ptr, sizeof(svoh_align_result) * (size_t)n_problems);
+  memcpy(results, ctx->aq.h_results.ptr, sizeof(svoh_align_result) * (size_t)n_problems);
   return SVOH_OK;
 } SVOH_ABI_CATCH(ctx)
 

@@ -15,6 +15,7 @@
 
 #include "../../include/svo_hip.h"
 #include "svoh_matcher_block.h"
+#include "svoh_align_block.h"
 
 namespace svoh {
 
@@ -183,6 +184,155 @@ struct PinnedBuffer {
   ~PinnedBuffer() { if (ptr) (void)hipHostFree(ptr); }
 };
 
+// The alignment's launch queue (sparse_align.hip): the staged blocks, the workspaces, the result queues, and the streams and
+// events of the three mechanisms a queued launch may use.  What a launch gets is decided by place_block / place_launch
+// (svoh_align_block.h) from `q`; the HIP objects here carry it out.  Everything outside sparse_align.hip reaches the queue
+// through join / sync_lanes / drain, the result look-up of the candidate projection, and create / teardown.
+struct AlignQueue {
+  hipStream_t main = nullptr;  // the context's stream: lane 0
+  AlignQueueState q;
+
+  // the staged blocks (svoh_align_block.h, AlignBlock)
+  DevBuffer d_desc[2];         // problem + camera descriptors, control words, uploaded feature arrays: the block of even launches and of odd ones (q.desc_slot)
+  PinnedBuffer h_desc;         // the pinned staging block of even launches ...
+  PinnedBuffer h_desc_odd;     // ... and of odd ones
+  PinnedBuffer& h_block(unsigned slot) { return slot ? h_desc_odd : h_desc; }
+  // The pinned staging blocks are reused.  A launch fetched before the next one is queued (the per-frame use) has
+  // drained the stream: nothing to protect, no event on the stream (an event record costs a launch 4.5 us of stream time,
+  // tools/svoh_call_overhead).  Launches queued back to back alternate between the two blocks; from the second one on
+  // each records ev_staged behind its upload, and the third and later wait for the event of the launch before them
+  // -- which lies behind the upload that last read their block.
+  hipEvent_t ev_staged = nullptr;
+  hipEvent_t staged_wait_ev() const
+  {
+    return q.staged_wait == kAlignWaitStaged ? ev_staged : q.staged_wait == kAlignWaitKernel0 ? ev_kernel[0] : q.staged_wait == kAlignWaitKernel1 ? ev_kernel[1] : nullptr;
+  }
+
+  // results of the launches queued since the last fetch, launch after launch in h_results
+  static constexpr size_t kMaxQueuedResults = (size_t)1 << 18;
+  DevBuffer d_results;         // svoh_align_result[n]
+  PinnedBuffer h_results;
+  DevBuffer d_eval;            // evaluate() outputs
+  int last_n = 0;              // what svoh_sparse_align_fetch may hand out
+  size_t pending_results = 0, last_results_off = 0;
+  // ... and on the device: every launch since the last fetch has its own block of d_results (pending_dev results are
+  // taken), so that a candidate projection queued behind SEVERAL launches can read the result of any of them;
+  // result_dev_index[k] = where result #k of the queue lives in d_results
+  size_t pending_dev = 0;
+  std::vector<uint32_t> result_dev_index;
+  bool has_queued_result(size_t k) const { return k < pending_results && k < result_dev_index.size() && d_results.ptr; }
+  const svoh_align_result* device_results() const { return static_cast<const svoh_align_result*>(d_results.ptr); }
+  uint32_t queued_result_index(size_t k) const { return result_dev_index[k]; }   // in device_results()
+  const svoh_align_result* queued_result(size_t k) const { return device_results() + result_dev_index[k]; }
+  // what svoh_memory_info counts of the queue's device buffers (the second lane's workspace has never been part of it)
+  size_t reported_device_bytes() const { return d_desc[0].cap + d_desc[1].cap + d_results.cap + d_feat.cap + d_eval.cap; }
+  bool has_lanes() const { return lane_stream != nullptr; }
+
+  // a ring of event pairs, one per alignment launch: callers that queue launches back to back (enqueue without
+  // fetch) can still read every launch's device time afterwards
+  static constexpr int kEventRing = 32;
+  hipEvent_t ev_start[kEventRing] = {}, ev_stop[kEventRing] = {};
+  unsigned long long launches = 0;
+  unsigned long long timed_launches = 0;   // alignment launches bracketed by events (ring slots in use)
+  bool last_timed = false;                 // ... and whether the most recent alignment launch was one of them
+  // what the most recent full-run alignment launch looked like (svoh_sparse_align_last_launch_info); key 0: none yet
+  int32_t last_geometry_key = 0, last_grid = 0, last_n_desc = 0;
+  int32_t last_lds_img_bytes = 0;   // ... and the LDS bytes its kernel had for the levels' images (svoh_sparse_align_last_launch_lds)
+  int32_t last_info_lane = 0;       // svoh_sparse_align_last_launch_lane: the lane of the most recent launch of the resident kernel (full run or evaluation)
+
+  // Side copies (sparse_align.hip, enqueue_align; SVOH_ALIGN_SIDE_COPIES=0 turns them off).  A batch launch queued behind an
+  // alignment launch that nobody has waited for uploads its block on copy_stream while that launch's kernel runs -- into the
+  // device block the kernel is not reading -- and its results travel to h_results on the same stream while the NEXT kernel runs:
+  //   copy stream:  wait(kernel N-2 done)  upload N  record(ev_uploaded)  record(ev_staged)  wait(kernel N-1 done)  results N-1  record(ev_delivered)
+  //   main:         wait(ev_uploaded)  kernel N  record(ev_kernel[slot])
+  // The copy of launch N's results is held back (download) until the next launch has put its upload on the copy stream --
+  // behind a wait for kernel N that upload would not run beside kernel N -- or until somebody drains.
+  hipStream_t copy_stream = nullptr;    // made by the context's first launch of the batch geometry (side_setup), never by a context of small or keyed launches
+  hipEvent_t ev_kernel[2] = {};         // on a lane behind a kernel that read d_desc[slot] (a side launch records its own; the launch behind an in-stream one records that one's); q.block_read[slot]: recorded since the last drain
+  hipEvent_t ev_uploaded = nullptr, ev_delivered = nullptr;
+  struct Download { void* dst = nullptr; const void* src = nullptr; size_t bytes = 0; hipEvent_t after = nullptr; } download;   // bytes == 0: none held back
+  bool delivery_pending = false;        // ev_delivered lies behind copies to h_results that nobody has waited for
+
+  // Launch lanes (sparse_align.hip, enqueue_align; SVOH_ALIGN_OVERLAP=0 turns them off).  A launch of the batch geometry queued
+  // right behind another one that nobody has waited for runs on the OTHER lane: its workgroups become resident one by one, as the
+  // workgroups of the launch before it leave their compute units, instead of all together once that launch has ended.  Lane 0 is
+  // `main` with `d_feat`, lane 1 lane_stream with d_feat_lane1 (each lane's kernels follow one another in stream order, so a
+  // lane's workspace has one user at a time; the queue head of a launch lies in its descriptor block, and launches that follow one
+  // another never share a block).  Two launches on different lanes share nothing but read-only inputs.
+  //   main:     record(ev_front)  [upload N]  kernel N                         kernel N+2
+  //   lane 1:   wait(ev_front)                 [upload N+1]  kernel N+1  record(ev_lane1)
+  // Everything else that puts work on `main`, or hands it out, calls join() first: `main` then waits for lane 1,
+  // and the next batch launch is the first of a new queue -- on lane 0, behind whatever was put there.
+  hipStream_t lane_stream = nullptr;    // made, like d_feat_lane1, by the context's first launch that takes lane 1
+  DevBuffer d_feat;                     // per-feature workspace (svoh_align_block.h, AlignWorkspace) of lane 0 ...
+  DevBuffer d_feat_lane1;               // ... and of lane 1
+  DevBuffer& workspace(int lane) { return lane ? d_feat_lane1 : d_feat; }
+  hipEvent_t ev_front = nullptr;        // on `main` in front of the first launch of a queue: what was there before it
+  hipEvent_t ev_lane1 = nullptr;        // on lane 1 behind its most recent launch
+  hipStream_t stream_of(int lane) const { return lane ? lane_stream : main; }
+
+  // the context's stream and the events every context has, in the order the context makes them
+  hipError_t create(hipStream_t context_stream)
+  {
+    main = context_stream;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < kEventRing; ++k) {
+      if (e == hipSuccess) e = hipEventCreate(&ev_start[k]);
+      if (e == hipSuccess) e = hipEventCreate(&ev_stop[k]);
+    }
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_staged, hipEventDisableTiming);
+    return e;
+  }
+  // Called by every entry that puts work on the context's stream, or hands that stream out, before it does.  The stream waits for
+  // the launch on lane 1, if there is one it has not waited for, and the queue of overlapped launches ends: the next alignment
+  // launch goes onto the context's stream, behind the caller's work.  Two flag tests when there is nothing to join.
+  hipError_t join()
+  {
+    q.chain = false;
+    if (!q.lane1_pending) return hipSuccess;
+    const hipError_t e = hipStreamWaitEvent(main, ev_lane1, 0);
+    if (e == hipSuccess) q.lane1_pending = false;
+    return e;
+  }
+  // the host waits for both lanes (svoh_synchronize): a launch on the second one is not on the context's stream
+  hipError_t sync_lanes()
+  {
+    hipError_t e = hipStreamSynchronize(main);
+    if (e != hipSuccess) return e;
+    if (lane_stream) {
+      e = hipStreamSynchronize(lane_stream);
+      if (e != hipSuccess) return e;
+      q.lane1_pending = false;
+    }
+    q.chain = false;
+    return hipSuccess;
+  }
+  // sparse_align.hip
+  hipError_t drain();            // every launch has run (its upload with it: the kernel waits for it) and every result is in h_results
+  hipError_t flush_download();   // the copy of a side launch's results that was held back goes onto the copy stream, behind that launch's kernel
+  hipError_t side_setup(void* h, void* d, size_t bytes);
+  hipError_t lane_setup(void* h, void* d, size_t bytes);
+  // the context goes: the streams of the queue run empty and go with their events (a copy that was held back is dropped)
+  // (both lanes first: a copy queued on the copy stream waits for an event behind a kernel on one of them)
+  void teardown()
+  {
+    if (lane_stream) { (void)hipStreamSynchronize(lane_stream); }
+    if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
+    if (lane_stream) { (void)hipStreamDestroy(lane_stream); }
+    for (hipEvent_t ev : { ev_kernel[0], ev_kernel[1], ev_uploaded, ev_delivered, ev_front, ev_lane1 })
+      if (ev) (void)hipEventDestroy(ev);
+  }
+  // ... and, behind the context's frames and masks as always, the events every context has
+  void destroy_events()
+  {
+    for (int k = 0; k < kEventRing; ++k) {
+      if (ev_start[k]) (void)hipEventDestroy(ev_start[k]);
+      if (ev_stop[k]) (void)hipEventDestroy(ev_stop[k]);
+    }
+    if (ev_staged) (void)hipEventDestroy(ev_staged);
+  }
+};
+
 }  // namespace svoh
 
 // Tuning and diagnostic knobs: read from the environment (SVOH_*) ONCE, when the context is made, and again only on
@@ -232,78 +382,9 @@ struct svoh_ctx {
   svoh::PinnedBuffer h_features;        // the upload's staging block ...
   hipEvent_t ev_features = nullptr;     // ... and what says its last copy has run (made at first use)
 
-  // sparse-align workspaces
-  svoh::DevBuffer d_desc[2];   // problem + camera descriptors, control words, uploaded feature arrays: the block of even launches and of odd ones (align_desc_slot)
-  svoh::DevBuffer d_results;   // svoh_align_result[n]
-  svoh::DevBuffer d_feat;      // per-feature workspace
-  svoh::DevBuffer d_eval;      // evaluate() outputs
+  svoh::AlignQueue aq;   // the alignment: its staged blocks, workspaces, result queues and launch queue
   svoh::DevBuffer d_xchg;      // cluster mode of the alignment: exchange slots + arrival counter
   svoh::DevBuffer d_split;     // svoh_sparse_align_split_buffers: a Gauss-Newton state + 74 sums
-  svoh::PinnedBuffer h_desc;           // the pinned staging block of even launches ...
-  svoh::PinnedBuffer h_desc_odd;       // ... and of odd ones (see align_launches_since_drain)
-  svoh::PinnedBuffer h_results;
-  int last_align_n = 0;
-  // results of the launches queued since the last fetch, launch after launch in h_results
-  static constexpr size_t kMaxQueuedResults = (size_t)1 << 18;
-  size_t align_pending_results = 0, align_last_results_off = 0;
-  // ... and on the device: every launch since the last fetch has its own block of d_results (align_pending_dev results are
-  // taken), so that a candidate projection queued behind SEVERAL launches can read the result of any of them;
-  // align_result_dev_index[k] = where result #k of the queue lives in d_results
-  size_t align_pending_dev = 0;
-  std::vector<uint32_t> align_result_dev_index;
-  // a ring of event pairs, one per alignment launch: callers that queue launches back to back (enqueue without
-  // fetch) can still read every launch's device time afterwards
-  static constexpr int kAlignEventRing = 32;
-  hipEvent_t ev_align_start[kAlignEventRing] = {}, ev_align_stop[kAlignEventRing] = {};
-  unsigned long long align_launches = 0;
-  // what the most recent full-run alignment launch looked like (svoh_sparse_align_last_launch_info); key 0: none yet
-  int32_t align_last_geometry_key = 0, align_last_grid = 0, align_last_n_desc = 0;
-  int32_t align_last_lds_img_bytes = 0;   // ... and the LDS bytes its kernel had for the levels' images (svoh_sparse_align_last_launch_lds)
-  // The pinned staging blocks are reused.  A launch fetched before the next one is queued (the per-frame use) has
-  // drained the stream: nothing to protect, no event on the stream (an event record costs a launch 4.5 us of stream time,
-  // tools/svoh_call_overhead).  Launches queued back to back alternate between the two blocks; from the second one on
-  // each records ev_align_staged behind its upload, and the third and later wait for the event of the launch before them
-  // -- which lies behind the upload that last read their block.
-  hipEvent_t ev_align_staged = nullptr;
-  hipEvent_t align_staged_wait_ev = nullptr;  // what the most recent launch recorded behind the upload of the launch before it (ev_align_staged, or see below); nullptr: nothing
-  unsigned align_launches_since_drain = 0;    // alignment launches queued since this file last waited for the stream
-  unsigned align_desc_slot = 0;
-  // Side copies (sparse_align.hip, enqueue_align; SVOH_ALIGN_SIDE_COPIES=0 turns them off).  A batch launch queued behind an
-  // alignment launch that nobody has waited for uploads its block on align_copy_stream while that launch's kernel runs -- into the
-  // device block the kernel is not reading -- and its results travel to h_results on the same stream while the NEXT kernel runs:
-  //   copy stream:  wait(kernel N-2 done)  upload N  record(ev_align_uploaded)  record(ev_align_staged)  wait(kernel N-1 done)  results N-1  record(ev_align_delivered)
-  //   ctx->stream:  wait(ev_align_uploaded)  kernel N  record(ev_align_kernel[slot])
-  // The copy of launch N's results is held back (align_download) until the next launch has put its upload on the copy stream --
-  // behind a wait for kernel N that upload would not run beside kernel N -- or until somebody drains (align_drain).
-  hipStream_t align_copy_stream = nullptr;    // made by the context's first launch of the batch geometry (align_side_setup), never by a context of small or keyed launches
-  hipEvent_t ev_align_kernel[2] = {};         // on ctx->stream behind a kernel that read d_desc[slot] (a side launch records its own; the launch behind an in-stream one records that one's)
-  hipEvent_t align_block_read_ev[2] = {};     // the event behind the last kernel that read d_desc[slot], if one was recorded since the last drain
-  hipEvent_t ev_align_uploaded = nullptr, ev_align_delivered = nullptr;
-  struct AlignDownload { void* dst = nullptr; const void* src = nullptr; size_t bytes = 0; hipEvent_t after = nullptr; } align_download;   // bytes == 0: none held back
-  bool align_delivery_pending = false;        // ev_align_delivered lies behind copies to h_results that nobody has waited for
-  bool align_last_was_side = false;           // the most recent launch uploaded on the copy stream
-  unsigned long long align_side_launches = 0; // launches that took the side path (read by svoh_test_align_side_launches of libsvo_hip_testhooks.so only)
-  // Launch lanes (sparse_align.hip, enqueue_align; SVOH_ALIGN_OVERLAP=0 turns them off).  A launch of the batch geometry queued
-  // right behind another one that nobody has waited for runs on the OTHER lane: its workgroups become resident one by one, as the
-  // workgroups of the launch before it leave their compute units, instead of all together once that launch has ended.  Lane 0 is
-  // `stream` with `d_feat`, lane 1 align_lane_stream with d_feat_lane1 (each lane's kernels follow one another in stream order, so a
-  // lane's workspace has one user at a time; the queue head of a launch lies in its descriptor block, and launches that follow one
-  // another never share a block).  Two launches on different lanes share nothing but read-only inputs.
-  //   ctx->stream:  record(ev_align_front)  [upload N]  kernel N                         kernel N+2
-  //   lane 1:       wait(ev_align_front)                 [upload N+1]  kernel N+1  record(ev_align_lane1)
-  // Everything else that puts work on `stream`, or hands `stream` out, calls align_join_lanes first: `stream` then waits for lane 1,
-  // and the next batch launch is the first of a new queue -- on lane 0, behind whatever was put there.
-  hipStream_t align_lane_stream = nullptr;    // made, like d_feat_lane1, by the context's first launch that takes lane 1
-  svoh::DevBuffer d_feat_lane1;
-  hipEvent_t ev_align_front = nullptr;        // on `stream` in front of the first launch of a queue: what was there before it
-  hipEvent_t ev_align_lane1 = nullptr;        // on lane 1 behind its most recent launch
-  bool align_lane1_pending = false;           // ... which `stream` has not waited for (and no host wait has covered)
-  bool align_lane1_wants_front = false;       // ev_align_front was recorded and lane 1 has not waited for it yet
-  bool align_chain = false;                   // the most recent work on either lane is a launch of the batch geometry that may be overlapped
-  int align_last_lane = 0;                    // the lane of the most recent alignment launch
-  unsigned long long align_lane1_launches = 0;
-  int32_t align_last_info_lane = 0;           // svoh_sparse_align_last_launch_lane: the lane of the most recent launch of the resident kernel (full run or evaluation)
-  hipStream_t align_stream_of(int lane) const { return lane ? align_lane_stream : stream; }
   bool align_shared_classes = false;   // svoh_set_align_geometry_classes
   bool align_no_cluster = false;   // svoh_sparse_align_batch repeating a launch whose cluster gave up
   hipEvent_t ev_misc_start = nullptr, ev_misc_stop = nullptr;  // KLT / matcher / seeds
@@ -316,8 +397,6 @@ struct svoh_ctx {
   bool upload_pending = false;           // ev_upload recorded and not yet waited for by the context's stream (svoh_prefetch_fence)
   bool misc_timed = false;     // the last KLT / matcher / seed / pose / detector launch was bracketed by the event pair
   bool misc_launched = false;  // ... has happened at all (its work counters exist)
-  unsigned long long align_timed_launches = 0;   // alignment launches bracketed by events (ring slots in use)
-  bool align_last_timed = false;                 // ... and whether the most recent alignment launch was one of them
   bool timing_on() const { return knobs.kernel_timing != kKnobUnset && knobs.kernel_timing != 0; }
   svoh::DevBuffer d_counters;  // 8 x uint64 work counters of the last KLT / matcher kernel
   svoh::DevBuffer d_unit_counts;  // 4 x uint32 per unit
@@ -425,18 +504,6 @@ hipError_t svoh_copy_to_host(svoh_ctx* ctx, void* dst_pinned, const void* src_de
 // against copyin_kernel_d2h_sync with SVOH_OVERHEAD_N_IN): 32 KB 27.4 / 24.7 us, 64 KB 33.7 / 29.0, 128 KB 48.8 / 37.9; 16 KB
 // 18.1 / 22.6 the other way round -- blocks of 32 KB .. 1 MB are read by a copy kernel, the rest goes through hipMemcpyAsync.
 hipError_t svoh_copy_to_device(svoh_ctx* ctx, void* dst_device, const void* src_pinned, size_t bytes, hipStream_t on = nullptr);
-// Launch lanes of the alignment (svoh_ctx): called by every entry that puts work on the context's stream, or hands that stream out,
-// before it does.  The stream waits for the launch on lane 1, if there is one it has not waited for, and the queue of overlapped
-// launches ends: the next alignment launch goes onto the context's stream, behind the caller's work.  Two flag tests when there is
-// nothing to join.
-inline hipError_t align_join_lanes(svoh_ctx* ctx)
-{
-  ctx->align_chain = false;
-  if (!ctx->align_lane1_pending) return hipSuccess;
-  const hipError_t e = hipStreamWaitEvent(ctx->stream, ctx->ev_align_lane1, 0);
-  if (e == hipSuccess) ctx->align_lane1_pending = false;
-  return e;
-}
 int reduce_unit_counts(svoh_ctx* ctx, size_t n_units);
 void set_global_error(const char* msg);
 const Frame* find_frame(const svoh_ctx* ctx, svoh_frame_t id);
@@ -476,7 +543,7 @@ __device__ __forceinline__ int wave_sum_i32_dpp(int v)
                              hipGetErrorString(svoh_e_), __FILE__, __LINE__);            \
   } while (0)
 
-#define SVOH_ALIGN_JOIN(ctx) SVOH_HIP_TRY(ctx, svoh::align_join_lanes(ctx))
+#define SVOH_ALIGN_JOIN(ctx) SVOH_HIP_TRY(ctx, (ctx)->aq.join())
 
 #define SVOH_REQUIRE(ctx, cond, msg)                                                     \
   do {                                                                                   \
